@@ -17,6 +17,13 @@ with their status.  Under a launcher, WORLD_SIZE must equal --gpus.
 Also: --config 3 (100M variable-length Zipf keys + 50M negative probes), --config 5 (1B x 32 B,
 15 bits/key -> m saturates at u32::MAX, k = 4; keys split over ranks, OR all-reduce, full
 probe sweep), --e2e (keys in host memory: H2D + build + D2H through the C ABI's pipeline).
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+result line (the roofline block comes from the timed steps' own per-phase events).  --full adds
+what takes runs of its own: the check that the last build holds every key, its fill ratio, the
+positive probe sweep per strategy, and the CPU baselines (the 1-thread port and the
+prefix-shared multi-thread port; also those of --sst and --compact).  --dump-outputs DIR writes
+the filter of the last timed step (see dump_filter) so two builds of the library can be compared.
 """
 import argparse
 import ctypes
@@ -26,6 +33,12 @@ import socket
 import subprocess
 import sys
 import time
+
+# --dump-outputs: the filter's u32 words are exact in float64; the whole filter can exceed the
+# 64 MB a dump may take, so it is written as a seeded sample of words plus per-block sums
+DUMP_SAMPLE = 4_000_000  # words (32 MB as float64)
+DUMP_BLOCK = 4096  # words per block sum (< 2^44: exact in float64)
+DUMP_SEED = 0x5EEDD0
 
 
 def make_parser():
@@ -59,7 +72,15 @@ def make_parser():
     ap.add_argument("--strategy", type=int, default=0, help="0 auto, 1 atomic, 2 partitioned")
     ap.add_argument("--separate-zero", action="store_true",
                     help="zero the filter with a fill kernel before each build instead of VBF_BUILD_FRESH")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the post-timing checks of the last "
+                         "build (every key found, fill ratio), the positive probe sweep per strategy, and the "
+                         "CPU baselines (configs 2/4, --sst, --compact)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the filter the last step built to DIR as float64 .npy "
+                         "(configs 2-5): a fixed, seeded sample of its words and the sum of every block of "
+                         "%d words" % DUMP_BLOCK)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-sample", type=int, default=10_000_000)
     ap.add_argument("--cpu-opt-threads", type=int, default=None,
                     help="threads of the prefix-shared CPU port (default: every usable host core)")
@@ -182,6 +203,29 @@ def vp(t):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_filter(ctx, args, words, nwords):
+    """--dump-outputs: the first `nwords` words of the int32 device tensor `words` -- the filter
+    the last timed step built, what the caller of the build receives -- as float64 .npy files in
+    args.dump_outputs.  words.npy holds the words at DUMP_SAMPLE seeded indices (the same indices
+    for the same filter size; the whole filter when it is smaller), words_block_sums.npy the sum of
+    every DUMP_BLOCK consecutive words, so that every word of the filter counts.  With several ranks the
+    files of rank r > 0 are named *_rank<r>.npy."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    w = words[:nwords].to(torch.int64) & 0xFFFFFFFF  # the u32 value of each int32 word
+    if nwords > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, nwords, size=DUMP_SAMPLE))
+        sample = w[torch.from_numpy(idx).to(w.device)]
+    else:
+        sample = w
+    pad = -nwords % DUMP_BLOCK
+    sums = torch.nn.functional.pad(w, (0, pad)).view(-1, DUMP_BLOCK).sum(dim=1)
+    tag = "" if ctx.rank == 0 else "_rank%d" % ctx.rank
+    for name, t in (("words", sample), ("words_block_sums", sums)):
+        np.save(os.path.join(args.dump_outputs, name + tag + ".npy"), t.cpu().numpy().astype(np.float64))
 
 
 class Ctx:
@@ -408,16 +452,20 @@ def bench_fixed(ctx, args):
 
     wall, kms, phases = timed_steps(ctx, step, args.steps, args.warmup)
     rank_wall = ctx.rank_wall
+    dump_filter(ctx, args, words, nwords)
 
-    # post-timing checks on the last build: every key present; fill ratio
-    cnt = torch.zeros(1, dtype=torch.int64, device=ctx.dev)
-    call("vbf_probe_count_dev", vp(keys), None, L, n, lp, m, k, vp(words), vp(cnt), ctx.sp)
-    pop = torch.zeros(1, dtype=torch.int64, device=ctx.dev)
-    call("vbf_popcount_dev", vp(words), nwords, vp(pop), ctx.sp)
-    torch.cuda.synchronize()
-    assert int(cnt.item()) == n, "false negatives: %d of %d keys found" % (cnt.item(), n)
-    sweep = time_probe_strategies(ctx, lambda st: call("vbf_probe_count_dev_ex", vp(keys), None, L, n, lp, m, k,
-                                                       vp(words), vp(cnt), st, ctx.sp))
+    fill_ratio = sweep = None
+    if args.full:
+        # post-timing checks on the last build: every key present; fill ratio
+        cnt = torch.zeros(1, dtype=torch.int64, device=ctx.dev)
+        call("vbf_probe_count_dev", vp(keys), None, L, n, lp, m, k, vp(words), vp(cnt), ctx.sp)
+        pop = torch.zeros(1, dtype=torch.int64, device=ctx.dev)
+        call("vbf_popcount_dev", vp(words), nwords, vp(pop), ctx.sp)
+        torch.cuda.synchronize()
+        assert int(cnt.item()) == n, "false negatives: %d of %d keys found" % (cnt.item(), n)
+        fill_ratio = int(pop.item()) / m
+        sweep = time_probe_strategies(ctx, lambda st: call("vbf_probe_count_dev_ex", vp(keys), None, L, n, lp, m,
+                                                           k, vp(words), vp(cnt), st, ctx.sp))
 
     total_keys = ctx.sum_over_ranks(n) * args.steps
     value = total_keys / wall
@@ -438,7 +486,7 @@ def bench_fixed(ctx, args):
                                            else (None, None, None))
     per_rank = ctx.gather({"rank": ctx.rank, "device": ctx.local, "keys": n, "seed": seed,
                            "keys_per_s": n * args.steps / rank_wall, "ms_per_step": rank_wall / args.steps * 1e3,
-                           "fill_ratio": int(pop.item()) / m})
+                           "fill_ratio": fill_ratio})
     cfg_name = ("config4: %d independent SSTable shards x %dM x %dB keys, one per GPU (compaction fan-in), "
                 "%d bits/key (m=%d, k=%d per shard)" % (ctx.world, n // 10**6, L, args.bits_per_key, m, k)
                 if args.config == 4 else
@@ -468,12 +516,12 @@ def bench_fixed(ctx, args):
                      "algorithmic_bytes_per_key": bytes_per_key,
                      "siprounds_per_key": (L + 8) // 8 + 5 * k,
                      "phases": ph},
-        "fill_ratio": int(pop.item()) / m,
+        "fill_ratio": fill_ratio,
         "positive_sweep_ms": sweep,
         "ranks": per_rank,
         "topology": ctx.topology,
     }
-    if ctx.world == 1 and ctx.rank == 0 and not args.no_cpu_baseline:
+    if args.full and ctx.world == 1 and ctx.rank == 0 and not args.no_cpu_baseline:
         ns = args.cpu_sample
         host = keys[: ns * L].cpu().numpy()
         info = host_cpu_info()
@@ -520,6 +568,7 @@ def bench_var(ctx, args):
             evs.append((a, b))
 
     wall, kms, phases = timed_steps(ctx, step, args.steps, args.warmup)
+    dump_filter(ctx, args, words, (m + 31) // 32)
     cnt = torch.zeros(1, dtype=torch.int64, device=ctx.dev)
 
     def probe(evs):
@@ -594,6 +643,7 @@ def bench_cfg5(ctx, args):
         or_allreduce_(buf, chunk)
 
     wall, kms, phases = timed_steps(ctx, step, args.steps, args.warmup)
+    dump_filter(ctx, args, buf, nwords)
     cnt = torch.zeros(1, dtype=torch.int64, device=ctx.dev)
 
     # the full positive sweep (contains() of every key, bf.rs:95-105): one untimed call (the AUTO
@@ -821,7 +871,7 @@ def bench_sst(ctx, args):
                            "data_gb_per_s": data.numel() * args.steps / dwall / 1e9,
                            "phases": phase_report(dph, args.steps)},
            "phases": phase_report(rph, args.steps)}
-    if ctx.world == 1 and ctx.rank == 0 and not args.no_cpu_baseline:
+    if args.full and ctx.world == 1 and ctx.rank == 0 and not args.no_cpu_baseline:
         import oracle
         ns = min(n, args.cpu_sample)
         host = data[: ns * (L + 17)].cpu().numpy()
@@ -884,7 +934,7 @@ def bench_compact(ctx, args):
            "merge_only": {"ms_per_step": mwall / args.steps * 1e3, "entries_per_s": total * args.steps / mwall,
                           "phases": phase_report(mph, args.steps)},
            "phases": phase_report(fph, args.steps)}
-    if ctx.world == 1 and ctx.rank == 0 and not args.no_cpu_baseline:
+    if args.full and ctx.world == 1 and ctx.rank == 0 and not args.no_cpu_baseline:
         import oracle
         ns = min(per, args.cpu_sample // nr)
         hk = np.concatenate([k.view(-1, L)[:ns].cpu().numpy().reshape(-1) for k in ks])
@@ -984,6 +1034,8 @@ def main():
         args.config = 2 if world == 1 else 4
     if args.plan_only:
         return plan_only(args, world)
+    if args.dump_outputs and (args.compact or args.multi or args.sst or args.e2e or args.memtable or args.fanout):
+        raise SystemExit("bench.py: --dump-outputs writes the filter of the build configs (2-5) only")
     ctx = Ctx(args)
     if args.config == 5:
         args.keys = args.keys or 1_000_000_000

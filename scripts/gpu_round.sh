@@ -29,7 +29,7 @@ for s in $STEPS; do
     measure)  # bench line, kernel stats (k = 10, 19), SQ / FETCH_SIZE / WRITE_SIZE passes per config
         B="python3 $ROOT/bench.py --no-cpu-baseline"
         SQ="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
-        run bench_default 420 python3 bench.py
+        run bench_default 420 python3 bench.py --full
         (cd /tmp && run prof10 300 rocprofv3 --kernel-trace --stats -d "$OUT/meas/prof10" -o run --output-format csv -- $B --steps 40 --warmup 5) || exit $?
         (cd /tmp && run prof19 300 rocprofv3 --kernel-trace --stats -d "$OUT/meas/prof19" -o run --output-format csv -- $B --steps 20 --warmup 3 --bits-per-key 19) || exit $?
         i=0
@@ -46,7 +46,7 @@ for s in $STEPS; do
     bench5ab) run bench_cfg5_ab 900 python bench.py --config 5 --steps 3 --warmup 1 --no-cpu-baseline --probe-ab ;;
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     pytest) run pytest_gpu 1200 python -u -m pytest tests -x -v -m gpu --timeout 120 --timeout-method thread ;;
-    bench)  run bench 600 python bench.py ;;
+    bench)  run bench 600 python bench.py --full ;;
     benchq)  run bench_quick 300 python bench.py --no-cpu-baseline ;;
     bench19) run bench_k19 300 python bench.py --no-cpu-baseline --bits-per-key 19 --steps 100 ;;
     k19tests) run pytest_k19 900 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_scale.py -x -v -m gpu -k "19 or config2" --timeout 600 --timeout-method thread ;;
@@ -91,8 +91,8 @@ for s in $STEPS; do
     bench3nolo) run bench_cfg3_nolo 600 env VBF_LEN_ORDER=0 python bench.py --config 3 --steps 5 --warmup 1 --no-cpu-baseline ;;
     bench3nostage) run bench_cfg3_nostage 600 env VBF_STAGE_KEYS=0 python bench.py --config 3 --steps 5 --warmup 1 --no-cpu-baseline ;;
     bench5) run bench_cfg5 900 python bench.py --config 5 --steps 3 --warmup 1 ;;
-    sst)    run bench_sst 600 python bench.py --sst --steps 5 --warmup 1 ;;
-    compact) run bench_compact 600 python bench.py --compact --steps 5 --warmup 1 ;;
+    sst)    run bench_sst 600 python bench.py --sst --full --steps 5 --warmup 1 ;;
+    compact) run bench_compact 600 python bench.py --compact --full --steps 5 --warmup 1 ;;
     multi)  run bench_multi 600 python bench.py --multi --steps 5 --warmup 1 ;;
     profmultigp) (cd /tmp && run profmultigp 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/profmultigp" -o run -- python3 "$ROOT/bench.py" --multi --steps 10 --warmup 2) || exit $? ;;
     probetest) run pytest_probe 900 python -u -m pytest tests/test_gpu_probe.py tests/test_gpu_parity.py -x -q -m gpu --timeout 300 --timeout-method thread ;;

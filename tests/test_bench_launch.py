@@ -35,6 +35,49 @@ def test_spawn_command():
     assert cmd[-5] == os.path.join(ROOT, "bench.py") and cmd[-4:] == ["--gpus", "4", "--steps", "3"]
 
 
+def test_full_and_dump_outputs_are_off_by_default():
+    import bench
+    a = bench.make_parser().parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    a = bench.make_parser().parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+@pytest.mark.parametrize("nwords", [5, 4096, 10_000])
+def test_dump_filter_writes_float64_words_and_block_sums(tmp_path, monkeypatch, nwords):
+    """--dump-outputs on a host tensor: a filter below the sample size is written whole, a larger
+    one as the same seeded sample every time; the block sums cover every word; values are the
+    words' u32 values, exact in float64."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    rng = np.random.default_rng(nwords)
+    u32 = rng.integers(0, 1 << 32, size=nwords + 3, dtype=np.uint64).astype(np.uint32)  # 3 words of padding
+    u32[0] = 0xFFFFFFFF  # a negative int32
+    words = torch.from_numpy(u32.view(np.int32))
+    args = types.SimpleNamespace(dump_outputs=str(tmp_path / "out"))
+    ctx = types.SimpleNamespace(rank=0)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 4096)
+    bench.dump_filter(ctx, args, words, nwords)
+    got = np.load(os.path.join(args.dump_outputs, "words.npy"))
+    sums = np.load(os.path.join(args.dump_outputs, "words_block_sums.npy"))
+    assert got.dtype == np.float64 and sums.dtype == np.float64
+    want = u32[:nwords].astype(np.float64)
+    if nwords <= 4096:
+        assert np.array_equal(got, want)
+    else:
+        idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, nwords, size=4096))
+        assert np.array_equal(got, want[idx])
+    pad = np.concatenate([want, np.zeros(-nwords % bench.DUMP_BLOCK)])
+    assert np.array_equal(sums, pad.reshape(-1, bench.DUMP_BLOCK).sum(axis=1))
+    ctx.rank = 1
+    bench.dump_filter(ctx, args, words, nwords)
+    assert np.array_equal(np.load(os.path.join(args.dump_outputs, "words_rank1.npy")), got)
+
+
 def _plan(args, env=None):
     e = dict(os.environ)
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
