@@ -29,6 +29,8 @@
  *   lazy filter rebuild                src/key_range/range.rs:117-128 -> vbf_filter_rebuild_from_sst_*
  *   KeyRange::filter_sstables_by_key_range src/key_range/range.rs:91-147 -> vbf_multi_probe_* (batch)
  *   SizedTierRunner::merge_ssts_in_buckets src/compactors/sized.rs:170-320 -> vbf_compact_merge_*
+ *   Table::write_to_file               src/sst/table.rs:287-324    -> vbf_sst_encode_dev / _host
+ *   one bucket, merge to files + filter src/compactors/sized.rs:170-200 -> vbf_compact_write_host
  *
  * Key batches.  `keys` holds the key bytes back to back.  When `offsets` is non-NULL it has
  * n+1 nondecreasing entries and key j is keys[offsets[j] .. offsets[j+1]) (positions are
@@ -71,7 +73,8 @@ int vbf_device_count(int* count);
 /* Kernel-phase timing with hipEvents on the launch streams (for bench.py's roofline):
  * phases 0 tile-sort, 1 transpose, 2 segment-OR (partitioned build), 3 atomic build, 4 probe,
  * 5 data.db walk, 6 data.db scan, 7 data.db emit, 8 compaction merge levels, 9 fold, 10 select,
- * 11 partitioned-probe pack, 12 probe segment test, 13 probe answers.
+ * 11 partitioned-probe pack, 12 probe segment test, 13 probe answers, 14 SST-encode tile tables,
+ * 15 encode table scan + block count, 16 index.db emit, 17 data.db emit.
  * vbf_profile_read synchronizes, returns per-phase summed ms and launch counts, and resets. */
 int vbf_profile_enable(int on);
 int vbf_profile_read(double* ms, uint64_t* launches, int nphases);
@@ -378,6 +381,37 @@ int vbf_sst_decode_host(const uint8_t* data, uint64_t len, const uint8_t* index,
                         uint64_t* created_ms, uint8_t* tombstones, uint64_t entries_cap,
                         uint64_t* n_out, int device);
 
+/* ---- SST data.db / index.db encode ----
+ * Table::write_to_file (src/sst/table.rs:287-324) on the device, the inverse of vbf_sst_decode_*:
+ * entries laid back to back, entry = u32 key_len | key | u32 value offset | i64 created_at ms | u8
+ * tombstone (Block::serialize, src/block/block_manager.rs:176-193), cut into blocks greedily -- a
+ * block takes the next entry unless size + (L + 17) > 4096 (Block::is_full, :159-161) -- and one
+ * index.db record per block, u32 key_len | key | u32 block_start with the block's LAST key
+ * (write_block, table.rs:333-340; Index::serialize_entry, src/index/indexer.rs:151-170).
+ * Keys in the layout of every entry point (offsets: n+1 absolute positions, offsets[0] need not be
+ * 0; or NULL with a fixed stride).  val_offsets / created_ms / tombstones may each be NULL (zeros
+ * are written); a tombstone byte != 0 is written as 1.  Key order is not checked.
+ * Outputs: data, index and blocks (the u32 block start offsets, what vbf_sst_decode_dev takes) may
+ * each be NULL; all three NULL is the size query.  *data_len, *index_len and *nblocks are always
+ * written, also when a capacity is too small (VBF_EINVAL, nothing written to the outputs).
+ * Capacities that always suffice: key bytes + 17 n, key bytes + 8 n, n.
+ * Synchronizes the stream once (the sizes; never with a fixed stride, whose blocks are closed-form);
+ * the output passes are left queued on it.  n == 0 is VBF_OK with zero sizes and no device work.
+ * VBF_EINVAL: a key longer than 4079 bytes (the reference fails the flush with BlockIsFull,
+ * block_manager.rs:121-125), descending offsets, or a data.db of 2^32 bytes or more (index.db's
+ * u32 block_start could not address it; the reference would truncate silently). */
+int vbf_sst_encode_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                       const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones,
+                       uint8_t* data, uint64_t data_cap, uint64_t* data_len,
+                       uint8_t* index, uint64_t index_cap, uint64_t* index_len,
+                       uint32_t* blocks, uint64_t blocks_cap, uint64_t* nblocks, void* stream);
+/* Same with every array in host memory, encoded on `device`.  Synchronous. */
+int vbf_sst_encode_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                        const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones,
+                        uint8_t* data, uint64_t data_cap, uint64_t* data_len,
+                        uint8_t* index, uint64_t index_cap, uint64_t* index_len,
+                        uint32_t* blocks, uint64_t blocks_cap, uint64_t* nblocks, int device);
+
 /* The lazy rebuild of src/key_range/range.rs:117-128 (load_entries_from_file then
  * build_filter_from_entries): decode data.db on the filter's device and OR every key into its
  * bits (len_prefix = 1), no_of_elements += n.  *n_out (may be NULL) = entries decoded.
@@ -450,6 +484,25 @@ int vbf_gather_entries_dev(const uint8_t* keys, const uint64_t* offsets, const i
                            uint64_t n, uint8_t* out_keys, uint64_t out_keys_cap, uint64_t* out_offsets,
                            int64_t* out_created_ms, uint8_t* out_tombstones, uint32_t* out_val_offsets,
                            uint64_t* key_bytes, void* stream);
+
+/* One bucket of merge_ssts_in_buckets (src/compactors/sized.rs:170-200) carried through to what
+ * Table::write_to_file writes (src/sst/table.rs:287-324): the arena (every input of
+ * vbf_compact_merge_host, plus the entries' value offsets, NULL = zeros) goes up once; the merge,
+ * the gather of the merged entries with their three per-entry arrays, the data.db / index.db
+ * encode and BloomFilter::new(false_positive, n) + build_filter_from_entries (sized.rs:192-193)
+ * all run on `device` with nothing returned to the host in between.  The two files (data / index
+ * may be NULL; capacities that always suffice: input key bytes + 17 entries and + 8 entries) and
+ * the tombstone-map updates come down; the filter stays device-resident in *filter_out (the
+ * caller frees it).  *n_out = merged entries.  An empty merge is VBF_EINVAL with *n_out = 0 and
+ * the map updates written: BloomFilter::new(p, 0) asserts (bf.rs:67).  Synchronous. */
+int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const int64_t* created_ms,
+                           const uint8_t* tombstones, const uint64_t* run_off, uint32_t nruns,
+                           const uint8_t* map_keys, const uint64_t* map_off, const int64_t* map_time,
+                           uint64_t map_n, int use_ttl, uint64_t entry_ttl_ms, uint64_t tombstone_ttl_ms,
+                           uint64_t now_ms, const uint32_t* val_offsets, double false_positive,
+                           vbf_filter** filter_out, uint8_t* data, uint64_t data_cap, uint64_t* data_len,
+                           uint8_t* index, uint64_t index_cap, uint64_t* index_len, uint64_t* n_out,
+                           uint32_t* upd_ids, int64_t* upd_time, uint64_t* n_upd, int device);
 
 #ifdef __cplusplus
 }

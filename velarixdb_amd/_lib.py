@@ -110,6 +110,13 @@ SIGNATURES = {
     "vbf_sst_index_blocks": (_int, [_vp, _u64, _vp, _u64, _vp]),
     "vbf_sst_decode_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     "vbf_sst_decode_host": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _int]),
+    "vbf_sst_encode_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
+                                   _vp]),
+    "vbf_sst_encode_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
+                                    _int]),
+    "vbf_compact_write_host": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _int, _u64, _u64, _u64,
+                                       _vp, _dbl, ctypes.POINTER(_vp), _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
+                                       _vp, _int]),
     "vbf_filter_rebuild_from_sst_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "vbf_filter_rebuild_from_sst_host": (_int, [_vp, _vp, _u64, _vp, _u64, _vp]),
 }
@@ -163,7 +170,8 @@ def device_count():
 
 
 PHASES = ("tile_sort", "transpose", "seg_or", "atomic_build", "probe", "sst_walk", "sst_scan", "sst_emit",
-          "merge_levels", "fold", "select", "probe_pack", "probe_seg", "probe_out")
+          "merge_levels", "fold", "select", "probe_pack", "probe_seg", "probe_out", "enc_tile", "enc_scan",
+          "enc_index", "enc_data")
 
 
 def profile_read():

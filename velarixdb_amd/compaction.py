@@ -8,6 +8,10 @@ Mirrors the merge half of SizedTierRunner (src/compactors/sized.rs):
       -> (SstEntries merged, BloomFilter)          the pairwise fold of merge_sstables (:207-283)
                                                    with tombstone_check (:286-320), then
                                                    BloomFilter::new(p, n) + build (:192-193)
+  .merge_bucket_sst(tables, now_ms)             the same bucket through to what Table::write_to_file
+      -> (data, index, BloomFilter, n)             writes (sst/table.rs:287-324): merge, gather, encode
+                                                   and filter build in one device pass
+                                                   (vbf_compact_write_host)
   .clear_tombstones()                           run_compaction's clear when nothing is left (:73-75)
   build_filters_sharded(batches, p, devices)    the fan-in's per-table filter builds (:192-193 for
                                                    every merged table), one table per device
@@ -23,7 +27,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import call
+from ._lib import VBF_EINVAL, call, check, lib
 from .filter import DEFAULT_FALSE_POSITIVE_RATE, BloomFilter
 from .keys import pack_offsets
 from .sst import SstEntries
@@ -106,6 +110,40 @@ class SizedTierMerger:
         bf = BloomFilter(self.config.filter_false_positive, len(merged), device=self.device)
         bf.set_batch(pack_offsets(merged.keys, merged.offsets))
         return merged, bf
+
+    def merge_bucket_sst(self, tables, now_ms=None):
+        """merge_ssts_in_buckets for one bucket, ending in files: (data.db bytes, index.db bytes,
+        the merged table's filter, merged entry count).  Merge, gather, encode and
+        BloomFilter::new(filter_false_positive, n) + build (sized.rs:192-193) run on the device
+        from one upload; self.tombstones is updated as merge_ids updates it."""
+        keys, offsets, created, tomb, val, run_off = _arena(tables)
+        total = int(run_off[-1])
+        mk = sorted(self.tombstones)
+        mkeys = np.frombuffer(b"".join(mk) or b"\0", np.uint8)
+        moff = np.concatenate([[0], np.cumsum([len(k) for k in mk], dtype=np.uint64)]).astype(np.uint64)
+        mtime = np.asarray([self.tombstones[k] for k in mk], np.int64)
+        kb = int(offsets[-1])
+        data = np.zeros(max(kb + 17 * total, 1), np.uint8)
+        index = np.zeros(max(kb + 8 * total, 1), np.uint8)
+        upd_ids = np.zeros(max(total, 1), np.uint32)
+        upd_t = np.zeros(max(total, 1), np.int64)
+        n_out, n_upd, dl, il = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        handle = ctypes.c_void_p()
+        now = int(time.time() * 1000) if now_ms is None else int(now_ms)
+        c = self.config
+        rc = lib.vbf_compact_write_host(
+            _p(keys), _p(offsets), _p(created), _p(tomb), run_off.ctypes.data, len(tables),
+            _p(mkeys) if mk else None, moff.ctypes.data if mk else None, _p(mtime), len(mk), int(c.use_ttl),
+            c.entry_ttl_ms, c.tombstone_ttl_ms, now, _p(val), c.filter_false_positive, ctypes.byref(handle),
+            data.ctypes.data, data.size, ctypes.byref(dl), index.ctypes.data, index.size, ctypes.byref(il),
+            ctypes.byref(n_out), upd_ids.ctypes.data, upd_t.ctypes.data, ctypes.byref(n_upd), self.device)
+        for e, t in zip(upd_ids[:n_upd.value].tolist(), upd_t[:n_upd.value].tolist()):
+            self.tombstones[keys[int(offsets[e]):int(offsets[e + 1])].tobytes()] = t
+        # an empty merge reaches BloomFilter::new(p, 0), whose assert fires (bf.rs:67)
+        if rc == VBF_EINVAL and lib.vbf_last_error().startswith(b"empty merge"):
+            raise AssertionError(lib.vbf_last_error().decode())
+        check("vbf_compact_write_host", rc)
+        return data[:dl.value].copy(), index[:il.value].copy(), BloomFilter(_handle=handle), n_out.value
 
 
 class _Shard(ctypes.Structure):

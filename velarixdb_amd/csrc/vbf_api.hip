@@ -160,6 +160,9 @@ enum WsSlot {
     kWsProbe = 9,
     kWsCount = 10,
     kWsMultiGroup = 11,
+    kWsSstEnc = 12,
+    kWsSstEncIO = 13,
+    kWsCompactOut = 14,
 };
 struct Workspace {
     int device;
@@ -1014,6 +1017,104 @@ int sst_emit_pass(vbf::SstArgs a, uint8_t* keys, uint64_t* offsets, uint32_t* va
     vbf::phase_begin(vbf::kPhaseSstEmit, s);
     HIP_TRY(vbf::sst_emit(a, s));
     vbf::phase_end(vbf::kPhaseSstEmit, s);
+    return VBF_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// SST data.db / index.db encode (vbf_sst_write.hip) on device pointers: the block segmentation
+// and the scan that places the index records, one readback (the sizes and the error word), then
+// the emit passes queued on the stream.  The three sizes are written whenever they are known,
+// so a too-small capacity still reports them.
+// ---------------------------------------------------------------------------------------
+int sst_encode(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, const uint32_t* val_off,
+               const int64_t* created, const uint8_t* tomb, uint8_t* data, uint64_t data_cap, uint64_t* data_len,
+               uint8_t* index, uint64_t index_cap, uint64_t* index_len, uint32_t* blocks, uint64_t blocks_cap,
+               uint64_t* nblocks, hipStream_t s) {
+    if (!data_len || !index_len || !nblocks) return fail(VBF_EINVAL, "data_len / index_len / nblocks is NULL");
+    *data_len = *index_len = *nblocks = 0;
+    if (n == 0) return VBF_OK;
+    constexpr uint64_t kMaxKey = 4096 - 17;
+    if (!offsets && stride > kMaxKey)
+        return fail(VBF_EINVAL, "entry of %llu bytes exceeds a 4096-byte block (BlockIsFull)",
+                    (unsigned long long)(stride + 17));
+    if (!keys && !offsets && stride) return fail(VBF_EINVAL, "keys is NULL");
+    if (n >= (1ull << 32) / 17)
+        return fail(VBF_EINVAL, "data.db of %llu entries reaches 2^32 bytes: index.db's u32 block offsets cannot address it",
+                    (unsigned long long)n);
+    vbf::SstEncArgs a{};
+    a.keys = keys;
+    a.offsets = offsets;
+    a.stride = stride;
+    a.n = n;
+    a.val_off = val_off;
+    a.created = created;
+    a.tomb = tomb;
+    uint64_t dl, il, nb;
+    if (!offsets) {  // equal entries: 4096 / (stride + 17) per block, nothing to compute on the device
+        const uint64_t es = stride + 17, per = 4096 / es;
+        dl = n * es;
+        nb = (n + per - 1) / per;
+        il = nb * (stride + 8);
+    } else {
+        a.ntiles = (n + vbf::kEncTile - 1) / vbf::kEncTile;
+        a.ngroups = (a.ntiles + vbf::kEncGroup - 1) / vbf::kEncGroup;
+        const uint64_t tiles_pad = a.ngroups * vbf::kEncGroup;
+        size_t tmpb = 0;
+        HIP_TRY(vbf::scan_u64(nullptr, &tmpb, nullptr, nullptr, a.ntiles + 1, s));
+        const uint64_t o_tab = align256(n), o_gtab = o_tab + align256(tiles_pad * vbf::kEncReach);
+        const uint64_t o_gep = o_gtab + align256(a.ngroups * vbf::kEncReach), o_ep = o_gep + align256(a.ngroups);
+        const uint64_t o_tsum = o_ep + align256(tiles_pad), o_tbase = o_tsum + align256((a.ntiles + 1) * 8);
+        const uint64_t o_err = o_tbase + align256((a.ntiles + 1) * 8), o_tmp = o_err + 256;
+        void* ws = nullptr;
+        int rc = get_workspace(s, o_tmp + tmpb, &ws, kWsSstEnc);
+        if (rc) return rc;
+        char* b = static_cast<char*>(ws);
+        a.delta = reinterpret_cast<uint8_t*>(b);
+        a.tab = reinterpret_cast<uint8_t*>(b + o_tab);
+        a.gtab = reinterpret_cast<uint8_t*>(b + o_gtab);
+        a.gep = reinterpret_cast<uint8_t*>(b + o_gep);
+        a.ep = reinterpret_cast<uint8_t*>(b + o_ep);
+        a.tsum = reinterpret_cast<uint64_t*>(b + o_tsum);
+        uint64_t* tbase = reinterpret_cast<uint64_t*>(b + o_tbase);
+        a.tbase = tbase;
+        a.err = reinterpret_cast<uint32_t*>(b + o_err);
+        HIP_TRY(hipMemsetAsync(a.err, 0, 4, s));
+        HIP_TRY(hipMemsetAsync(a.err + 1, 0xFF, 4, s));
+        HIP_TRY(hipMemsetAsync(a.tsum + a.ntiles, 0, 8, s));
+        HIP_TRY(vbf::sst_enc_segment(a, s));
+        HIP_TRY(vbf::scan_u64(b + o_tmp, &tmpb, a.tsum, tbase, a.ntiles + 1, s));
+        vbf::phase_end(vbf::kPhaseEncScan, s);
+        uint64_t tot = 0, oe[2] = {0, 0};
+        uint32_t ev[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(&tot, tbase + a.ntiles, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&oe[0], offsets, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&oe[1], offsets + n, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ev, a.err, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (ev[0] & vbf::kEncErrOrder) return fail(VBF_EINVAL, "offsets descend at entry %u", ev[1]);
+        if (ev[0] & vbf::kEncErrBig)
+            return fail(VBF_EINVAL, "entry %u exceeds a 4096-byte block (BlockIsFull): keys hold at most 4079 bytes", ev[1]);
+        dl = (oe[1] - oe[0]) + 17 * n;
+        nb = tot >> 40;
+        il = tot & ((1ull << 40) - 1);
+    }
+    if (dl >= (1ull << 32))
+        return fail(VBF_EINVAL, "data.db of %llu bytes reaches 2^32: index.db's u32 block offsets cannot address it",
+                    (unsigned long long)dl);
+    if (!keys && dl > 17 * n) return fail(VBF_EINVAL, "keys is NULL");
+    *data_len = dl;
+    *index_len = il;
+    *nblocks = nb;
+    if (data && data_cap < dl)
+        return fail(VBF_EINVAL, "data holds %llu < %llu bytes", (unsigned long long)data_cap, (unsigned long long)dl);
+    if (index && index_cap < il)
+        return fail(VBF_EINVAL, "index holds %llu < %llu bytes", (unsigned long long)index_cap, (unsigned long long)il);
+    if (blocks && blocks_cap < nb)
+        return fail(VBF_EINVAL, "blocks holds %llu < %llu offsets", (unsigned long long)blocks_cap, (unsigned long long)nb);
+    a.data = data;
+    a.index = index;
+    a.blocks = blocks;
+    if (data || index || blocks) HIP_TRY(vbf::sst_enc_emit(a, s));
     return VBF_OK;
 }
 
@@ -2259,6 +2360,74 @@ int vbf_sst_decode_host(const uint8_t* data, uint64_t len, const uint8_t* index,
     return ok();
 }
 
+// ---- SST data.db / index.db encode ----
+
+int vbf_sst_encode_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                       const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones, uint8_t* data,
+                       uint64_t data_cap, uint64_t* data_len, uint8_t* index, uint64_t index_cap, uint64_t* index_len,
+                       uint32_t* blocks, uint64_t blocks_cap, uint64_t* nblocks, void* stream) {
+    FORK_GUARD();
+    int rc = sst_encode(keys, offsets, stride, n, val_offsets, created_ms, tombstones, data, data_cap, data_len, index,
+                        index_cap, index_len, blocks, blocks_cap, nblocks, (hipStream_t)stream);
+    return rc ? rc : ok();
+}
+
+int vbf_sst_encode_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                        const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones, uint8_t* data,
+                        uint64_t data_cap, uint64_t* data_len, uint8_t* index, uint64_t index_cap, uint64_t* index_len,
+                        uint32_t* blocks, uint64_t blocks_cap, uint64_t* nblocks, int device) {
+    if (!data_len || !index_len || !nblocks) return fail(VBF_EINVAL, "data_len / index_len / nblocks is NULL");
+    *data_len = *index_len = *nblocks = 0;
+    if (n == 0) return ok();
+    if (!offsets && stride > 4079)
+        return fail(VBF_EINVAL, "entry of %llu bytes exceeds a 4096-byte block (BlockIsFull)",
+                    (unsigned long long)(stride + 17));
+    if (offsets && offsets[n] < offsets[0]) return fail(VBF_EINVAL, "offsets descend (last below first)");
+    const uint64_t k0 = offsets ? offsets[0] : 0, kb = offsets ? offsets[n] - k0 : n * stride;
+    if (!keys && kb) return fail(VBF_EINVAL, "keys is NULL");
+    if (n >= (1ull << 32) / 17 || kb >= (1ull << 32))
+        return fail(VBF_EINVAL, "data.db reaches 2^32 bytes: index.db's u32 block offsets cannot address it");
+    DEVICE_SCOPE(device);
+    hipStream_t s;
+    int rc = filter_stream(device, &s);
+    if (rc) return rc;
+    // device image: keys | offsets | val | created | tombstones | data | index | blocks, the outputs
+    // at the sizes that always suffice (or the caller's capacity when that is smaller)
+    const uint64_t dcap = data ? std::min(data_cap, kb + 17 * n) : 0, icap = index ? std::min(index_cap, kb + 8 * n) : 0;
+    const uint64_t bcap = blocks ? std::min(blocks_cap, n) : 0;
+    const uint64_t o_off = align256(kb), o_val = o_off + align256(offsets ? (n + 1) * 8 : 0);
+    const uint64_t o_cr = o_val + align256(val_offsets ? n * 4 : 0), o_tb = o_cr + align256(created_ms ? n * 8 : 0);
+    const uint64_t o_data = o_tb + align256(tombstones ? n : 0), o_idx = o_data + align256(dcap);
+    const uint64_t o_blk = o_idx + align256(icap), bytes = o_blk + align256(bcap * 4);
+    void* ws = nullptr;
+    if ((rc = get_workspace(s, bytes, &ws, kWsSstEncIO))) return rc;
+    char* b = static_cast<char*>(ws);
+    if (kb) HIP_TRY(hipMemcpyAsync(b, keys + k0, kb, hipMemcpyHostToDevice, s));
+    if (offsets) HIP_TRY(hipMemcpyAsync(b + o_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (val_offsets) HIP_TRY(hipMemcpyAsync(b + o_val, val_offsets, n * 4, hipMemcpyHostToDevice, s));
+    if (created_ms) HIP_TRY(hipMemcpyAsync(b + o_cr, created_ms, n * 8, hipMemcpyHostToDevice, s));
+    if (tombstones) HIP_TRY(hipMemcpyAsync(b + o_tb, tombstones, n, hipMemcpyHostToDevice, s));
+    // offsets are absolute positions in `keys`: the device copy starts at keys + offsets[0]
+    const uint8_t* d_keys = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(b) - k0);
+    uint8_t* d_data = data ? reinterpret_cast<uint8_t*>(b + o_data) : nullptr;
+    uint8_t* d_idx = index ? reinterpret_cast<uint8_t*>(b + o_idx) : nullptr;
+    uint32_t* d_blk = blocks ? reinterpret_cast<uint32_t*>(b + o_blk) : nullptr;
+    rc = sst_encode(d_keys, offsets ? reinterpret_cast<const uint64_t*>(b + o_off) : nullptr, stride, n,
+                    val_offsets ? reinterpret_cast<const uint32_t*>(b + o_val) : nullptr,
+                    created_ms ? reinterpret_cast<const int64_t*>(b + o_cr) : nullptr,
+                    tombstones ? reinterpret_cast<const uint8_t*>(b + o_tb) : nullptr, d_data, dcap, data_len, d_idx, icap,
+                    index_len, d_blk, bcap, nblocks, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);  // the uploads read the caller's buffers
+        return rc;
+    }
+    if (data && *data_len) HIP_TRY(hipMemcpyAsync(data, d_data, *data_len, hipMemcpyDeviceToHost, s));
+    if (index && *index_len) HIP_TRY(hipMemcpyAsync(index, d_idx, *index_len, hipMemcpyDeviceToHost, s));
+    if (blocks && *nblocks) HIP_TRY(hipMemcpyAsync(blocks, d_blk, *nblocks * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return ok();
+}
+
 // range.rs:117-128 (load_entries_from_file + build_filter_from_entries) on the device: decode
 // data.db into packed keys/offsets and OR their bits into the filter; no_of_elements += n.
 // Caller holds s.mu (drained), on s.device; the filter is device-resident.
@@ -2948,6 +3117,116 @@ int vbf_compact_merge_host(const uint8_t* keys, const uint64_t* offsets, const i
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (n_upd) *n_upd = nu;
+    return ok();
+}
+
+// One bucket through to the merged table's files and filter: merge -> gather -> encode -> build,
+// all on `device` from one upload of the arena.
+int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const int64_t* created_ms,
+                           const uint8_t* tombstones, const uint64_t* run_off, uint32_t nruns, const uint8_t* map_keys,
+                           const uint64_t* map_off, const int64_t* map_time, uint64_t map_n, int use_ttl,
+                           uint64_t entry_ttl_ms, uint64_t tombstone_ttl_ms, uint64_t now_ms,
+                           const uint32_t* val_offsets, double false_positive, vbf_filter** filter_out, uint8_t* data,
+                           uint64_t data_cap, uint64_t* data_len, uint8_t* index, uint64_t index_cap,
+                           uint64_t* index_len, uint64_t* n_out, uint32_t* upd_ids, int64_t* upd_time, uint64_t* n_upd,
+                           int device) {
+    if (!n_out || !data_len || !index_len || !filter_out) return fail(VBF_EINVAL, "NULL argument");
+    *n_out = *data_len = *index_len = 0;
+    *filter_out = nullptr;
+    if (n_upd) *n_upd = 0;
+    if (nruns && !run_off) return fail(VBF_EINVAL, "run_off is NULL");
+    const uint64_t total = nruns ? run_off[nruns] : 0;
+    if (total == 0) return fail(VBF_EINVAL, "empty merge: BloomFilter::new asserts no_of_elements > 0 (bf.rs:67)");
+    if (!offsets || !created_ms || !tombstones) return fail(VBF_EINVAL, "NULL argument");
+    if (map_n && (!map_keys || !map_off || !map_time)) return fail(VBF_EINVAL, "map arrays are NULL");
+    uint32_t m_probe, k_probe;  // bf.rs:63-66: the rate is checked before any work
+    int rc = vbf_size(false_positive, total, &m_probe, &k_probe);
+    if (rc) return rc;
+    DEVICE_SCOPE(device);
+    hipStream_t s;
+    if ((rc = filter_stream(device, &s))) return rc;
+    const bool want_upd = upd_ids && upd_time;
+    const uint64_t kb = offsets[total], mkb = map_n ? map_off[map_n] : 0;
+    const uint64_t o_off = align256(kb), o_cr = o_off + align256((total + 1) * 8), o_tb = o_cr + align256(total * 8);
+    const uint64_t o_val = o_tb + align256(total), o_mk = o_val + align256(total * 4), o_mo = o_mk + align256(mkb);
+    const uint64_t o_mt = o_mo + align256((map_n + 1) * 8), o_ids = o_mt + align256(map_n * 8);
+    const uint64_t o_ui = o_ids + align256(total * 4), o_ut = o_ui + align256(total * 4);
+    const uint64_t bytes = o_ut + align256(total * 8);
+    void* ws = nullptr;
+    if ((rc = get_workspace(s, bytes, &ws, kWsCompactIn))) return rc;
+    char* b = static_cast<char*>(ws);
+    if (kb) HIP_TRY(hipMemcpyAsync(b, keys, kb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b + o_off, offsets, (total + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b + o_cr, created_ms, total * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b + o_tb, tombstones, total, hipMemcpyHostToDevice, s));
+    if (val_offsets) HIP_TRY(hipMemcpyAsync(b + o_val, val_offsets, total * 4, hipMemcpyHostToDevice, s));
+    else HIP_TRY(hipMemsetAsync(b + o_val, 0, total * 4, s));
+    if (map_n) {
+        if (mkb) HIP_TRY(hipMemcpyAsync(b + o_mk, map_keys, mkb, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b + o_mo, map_off, (map_n + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b + o_mt, map_time, map_n * 8, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint8_t* a_keys = reinterpret_cast<const uint8_t*>(b);
+    const uint64_t* a_off = reinterpret_cast<const uint64_t*>(b + o_off);
+    const int64_t* a_cr = reinterpret_cast<const int64_t*>(b + o_cr);
+    const uint8_t* a_tb = reinterpret_cast<const uint8_t*>(b + o_tb);
+    const uint32_t* a_val = reinterpret_cast<const uint32_t*>(b + o_val);
+    const uint32_t* d_ids = reinterpret_cast<const uint32_t*>(b + o_ids);
+    uint64_t n = 0, nu = 0;
+    rc = compact_merge(a_keys, a_off, a_cr, a_tb, run_off, nruns, map_n ? reinterpret_cast<const uint8_t*>(b + o_mk) : nullptr,
+                       map_n ? reinterpret_cast<const uint64_t*>(b + o_mo) : nullptr,
+                       map_n ? reinterpret_cast<const int64_t*>(b + o_mt) : nullptr, map_n, use_ttl, entry_ttl_ms,
+                       tombstone_ttl_ms, now_ms, reinterpret_cast<uint32_t*>(b + o_ids), &n,
+                       want_upd ? reinterpret_cast<uint32_t*>(b + o_ui) : nullptr,
+                       want_upd ? reinterpret_cast<int64_t*>(b + o_ut) : nullptr, &nu, s);
+    if (rc) return rc;
+    // the map updates happen during the fold, before the merged table is looked at (sized.rs:286-320)
+    if (want_upd && nu) {
+        HIP_TRY(hipMemcpyAsync(upd_ids, b + o_ui, nu * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(upd_time, b + o_ut, nu * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (n_upd) *n_upd = nu;
+    if (n == 0) return fail(VBF_EINVAL, "empty merge: BloomFilter::new asserts no_of_elements > 0 (bf.rs:67)");
+    // merged table in the build's key layout, then its files; capacities that always suffice
+    const uint64_t q_off = align256(kb), q_cr = q_off + align256((n + 1) * 8), q_tb = q_cr + align256(n * 8);
+    const uint64_t q_val = q_tb + align256(n), q_data = q_val + align256(n * 4), q_idx = q_data + align256(kb + 17 * n);
+    const uint64_t q_end = q_idx + align256(kb + 8 * n);
+    void* ows = nullptr;
+    if ((rc = get_workspace(s, q_end, &ows, kWsCompactOut))) return rc;
+    char* q = static_cast<char*>(ows);
+    uint8_t* g_keys = reinterpret_cast<uint8_t*>(q);
+    uint64_t* g_off = reinterpret_cast<uint64_t*>(q + q_off);
+    uint64_t gkb = 0;
+    if ((rc = gather_entries(a_keys, a_off, a_cr, a_tb, a_val, d_ids, n, g_keys, kb, g_off,
+                             reinterpret_cast<int64_t*>(q + q_cr), reinterpret_cast<uint8_t*>(q + q_tb),
+                             reinterpret_cast<uint32_t*>(q + q_val), &gkb, s)))
+        return rc;
+    uint8_t* d_data = reinterpret_cast<uint8_t*>(q + q_data);
+    uint8_t* d_idx = reinterpret_cast<uint8_t*>(q + q_idx);
+    uint64_t nb = 0;
+    if ((rc = sst_encode(g_keys, g_off, 0, n, reinterpret_cast<const uint32_t*>(q + q_val),
+                         reinterpret_cast<const int64_t*>(q + q_cr), reinterpret_cast<const uint8_t*>(q + q_tb),
+                         data ? d_data : nullptr, kb + 17 * n, data_len, index ? d_idx : nullptr, kb + 8 * n, index_len,
+                         nullptr, 0, &nb, s)))
+        return rc;
+    *n_out = n;
+    if (data && data_cap < *data_len)
+        return fail(VBF_EINVAL, "data holds %llu < %llu bytes", (unsigned long long)data_cap,
+                    (unsigned long long)*data_len);
+    if (index && index_cap < *index_len)
+        return fail(VBF_EINVAL, "index holds %llu < %llu bytes", (unsigned long long)index_cap,
+                    (unsigned long long)*index_len);
+    // BloomFilter::new(false_positive, n) + build_filter_from_entries (sized.rs:192-193)
+    vbf_filter* f = nullptr;
+    if ((rc = vbf_filter_new(false_positive, n, device, &f))) return rc;
+    std::unique_ptr<vbf_filter> hold(f);  // freed on any failure below
+    if ((rc = vbf_filter_set_dev(f, g_keys, g_off, 0, n, 1, s))) return rc;
+    if (data && *data_len) HIP_TRY(hipMemcpyAsync(data, d_data, *data_len, hipMemcpyDeviceToHost, s));
+    if (index && *index_len) HIP_TRY(hipMemcpyAsync(index, d_idx, *index_len, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *filter_out = hold.release();
     return ok();
 }
 

@@ -30,7 +30,8 @@ hipError_t launch_build(const KeyBatch& kb, uint32_t m, uint32_t k, uint32_t* wo
 enum Phase { kPhaseTileSort = 0, kPhaseTranspose = 1, kPhaseSegOr = 2, kPhaseAtomicBuild = 3,
              kPhaseProbe = 4, kPhaseSstWalk = 5, kPhaseSstScan = 6, kPhaseSstEmit = 7,
              kPhaseMergeLevels = 8, kPhaseFold = 9, kPhaseSelect = 10, kPhaseProbePack = 11,
-             kPhaseProbeSeg = 12, kPhaseProbeOut = 13, kNumPhases = 14 };
+             kPhaseProbeSeg = 12, kPhaseProbeOut = 13, kPhaseEncTile = 14, kPhaseEncScan = 15,
+             kPhaseEncIndex = 16, kPhaseEncData = 17, kNumPhases = 18 };
 void phase_begin(int phase, hipStream_t s);
 void phase_end(int phase, hipStream_t s);
 
@@ -105,6 +106,36 @@ hipError_t sst_len_range(const uint32_t* lmin, const uint32_t* lmax, uint64_t nb
                          size_t* tmp_bytes, hipStream_t s);
 hipError_t sst_scan(const uint32_t* counts, uint64_t* ebase, uint64_t nblocks, void* tmp, size_t* tmp_bytes,
                     hipStream_t s);
+// SST data.db / index.db encode (vbf_sst_write.hip).  Entry j = key j plus val_off / created / tomb
+// (each may be NULL: zeros).  With offsets the blocks come from the tile-table segmentation
+// (sst_enc_segment, then an exclusive scan of tsum into tbase); with a fixed stride they are
+// closed-form and only sst_enc_emit runs.
+constexpr uint32_t kEncTile = 1024;   // entries per tile
+constexpr uint32_t kEncReach = 240;   // entries a block can hold at most (4096 / 17)
+constexpr uint32_t kEncGroup = 128;   // tiles per group
+enum : uint32_t { kEncErrOrder = 1, kEncErrBig = 2 };
+struct SstEncArgs {
+    const uint8_t* keys;
+    const uint64_t* offsets;  // n + 1 absolute positions, or NULL for `stride`
+    uint64_t stride, n;
+    const uint32_t* val_off;
+    const int64_t* created;
+    const uint8_t* tomb;
+    uint64_t ntiles, ngroups;
+    uint8_t* delta;         // [n] entries in the block that would start at entry e
+    uint8_t* tab;           // [ngroups * kEncGroup][kEncReach] tile transfer tables
+    uint8_t* gtab;          // [ngroups][kEncReach] group transfer tables
+    uint8_t* gep;           // [ngroups] entry point of each group's first tile
+    uint8_t* ep;            // [ngroups * kEncGroup] entry point of each tile
+    uint64_t* tsum;         // [ntiles + 1] per tile: blocks << 40 | index.db bytes
+    const uint64_t* tbase;  // [ntiles + 1] exclusive scan of tsum
+    uint32_t* err;          // [0] kEncErr bits, [1] first bad entry
+    uint8_t* data;          // outputs, each may be NULL
+    uint8_t* index;
+    uint32_t* blocks;
+};
+hipError_t sst_enc_segment(const SstEncArgs& a, hipStream_t s);
+hipError_t sst_enc_emit(const SstEncArgs& a, hipStream_t s);
 // Batched probe across SSTs (vbf_multi.hip).
 struct MultiSst {
     const uint32_t* words;

@@ -12,6 +12,9 @@ index.db already records (src/index/indexer.rs:151-170, src/sst/table.rs:331-338
                                                   and unique, as in the reference's SkipMap)
   load_entries_from_dir(sst_dir) -> SstEntries   Table::load_entries_from_file (table.rs:197-205)
   index_blocks(index)            -> u32 offsets  one per block
+  write_entries(entries)         -> (data, index) Table::write_to_file (table.rs:287-324), encoded on
+                                                  the device (velarixdb_amd/csrc/vbf_sst_write.hip)
+  write_sst_files(sst_dir, entries)              the same into sst_dir/data.db and index.db
   BloomFilter.rebuild_from_sst(data, index)      range.rs:117-128, see filter.py
 """
 import ctypes
@@ -98,3 +101,39 @@ def read_sst_files(sst_dir):
 def load_entries_from_dir(sst_dir, device=0):
     """Table::load_entries_from_file (sst/table.rs:197-205) for the SST directory `sst_dir`."""
     return load_entries(*read_sst_files(sst_dir), device=device)
+
+
+def write_entries(entries, device=0):
+    """Table::write_to_file (sst/table.rs:287-324) for `entries`, encoded on `device`:
+    (data.db bytes, index.db bytes) as numpy u8 arrays.  A key over 4079 bytes raises VbfError
+    where the reference fails the flush with BlockIsFull."""
+    n = len(entries)
+    if n == 0:
+        return np.zeros(0, np.uint8), np.zeros(0, np.uint8)
+    keys = np.ascontiguousarray(entries.keys, dtype=np.uint8)
+    offsets = np.ascontiguousarray(entries.offsets, dtype=np.uint64)
+    val = np.ascontiguousarray(entries.val_offsets, dtype=np.uint32)
+    created = np.ascontiguousarray(entries.created_ms).astype(np.int64, copy=False)
+    tomb = np.ascontiguousarray(entries.tombstones).astype(np.uint8)
+    kb = int(offsets[-1]) - int(offsets[0])
+    data = np.zeros(kb + 17 * n, dtype=np.uint8)
+    index = np.zeros(kb + 8 * n, dtype=np.uint8)
+    dl, il, nb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    vp = lambda x: x.ctypes.data if x.size else None
+    call("vbf_sst_encode_host", vp(keys), offsets.ctypes.data, 0, n, vp(val), vp(created), vp(tomb),
+         data.ctypes.data, data.size, ctypes.byref(dl), index.ctypes.data, index.size, ctypes.byref(il),
+         None, 0, ctypes.byref(nb), device)
+    assert dl.value == data.size
+    return data, index[:il.value].copy()
+
+
+def write_sst_files(sst_dir, entries, device=0):
+    """The inverse of read_sst_files / load_entries_from_dir: data.db and index.db of `entries`
+    written into `sst_dir` (created when missing)."""
+    data, index = write_entries(entries, device=device)
+    os.makedirs(sst_dir, exist_ok=True)
+    with open(os.path.join(sst_dir, DATA_FILE_NAME + ".db"), "wb") as f:
+        f.write(data.tobytes())
+    with open(os.path.join(sst_dir, INDEX_FILE_NAME + ".db"), "wb") as f:
+        f.write(index.tobytes())
+    return data, index
