@@ -31,6 +31,11 @@
  *   SizedTierRunner::merge_ssts_in_buckets src/compactors/sized.rs:170-320 -> vbf_compact_merge_*
  *   Table::write_to_file               src/sst/table.rs:287-324    -> vbf_sst_encode_dev / _host
  *   one bucket, merge to files + filter src/compactors/sized.rs:170-200 -> vbf_compact_write_host
+ *   Index::get                         src/index/indexer.rs:170-172 -> vbf_table_get_* (index step)
+ *   IndexFileNode::get_from_index      src/fs/mod.rs:667-710       -> vbf_table_get_* (index step)
+ *   Table::get                         src/sst/table.rs:184-193    -> vbf_table_get_* (block step)
+ *   DataFileNode::find_entry           src/fs/mod.rs:334-389       -> vbf_table_get_* (block step)
+ *   DataStore::search_key_in_sstables  src/db/store.rs:579-612     -> vbf_table_open_* + vbf_table_get_*
  *
  * Key batches.  `keys` holds the key bytes back to back.  When `offsets` is non-NULL it has
  * n+1 nondecreasing entries and key j is keys[offsets[j] .. offsets[j+1]) (positions are
@@ -74,7 +79,8 @@ int vbf_device_count(int* count);
  * phases 0 tile-sort, 1 transpose, 2 segment-OR (partitioned build), 3 atomic build, 4 probe,
  * 5 data.db walk, 6 data.db scan, 7 data.db emit, 8 compaction merge levels, 9 fold, 10 select,
  * 11 partitioned-probe pack, 12 probe segment test, 13 probe answers, 14 SST-encode tile tables,
- * 15 encode table scan + block count, 16 index.db emit, 17 data.db emit.
+ * 15 encode table scan + block count, 16 index.db emit, 17 data.db emit, 18 table open (side
+ * tables + validation), 19 table get.
  * vbf_profile_read synchronizes, returns per-phase summed ms and launch counts, and resets. */
 int vbf_profile_enable(int on);
 int vbf_profile_read(double* ms, uint64_t* launches, int nphases);
@@ -503,6 +509,82 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
                            vbf_filter** filter_out, uint8_t* data, uint64_t data_cap, uint64_t* data_len,
                            uint8_t* index, uint64_t index_cap, uint64_t* index_len, uint64_t* n_out,
                            uint32_t* upd_ids, int64_t* upd_time, uint64_t* n_upd, int device);
+
+/* ---- batched point lookups in SST tables ----
+ * The read path after the filters: per key and candidate SST the reference scans index.db for the
+ * first record whose key is >= the searched key (Index::get, src/index/indexer.rs:170-172;
+ * IndexFileNode::get_from_index, src/fs/mod.rs:667-710), scans data.db from that block's offset for
+ * an equal key (Table::get, src/sst/table.rs:184-193; DataFileNode::find_entry, src/fs/mod.rs:334-389)
+ * and keeps the strictly newest hit over the SSTs (DataStore::search_key_in_sstables,
+ * src/db/store.rs:579-612).  Here a table is opened once on the device and a batch of keys is
+ * looked up in every table in one launch; only the value-log read is left to the host.
+ *
+ * A vbf_table holds data.db, index.db and the block starts on the device plus side tables built at
+ * open (every block's entry starts and count, the start of every index record).  Open validates the
+ * files once; VBF_EINVAL, with the first offending block or entry in vbf_last_error(), for
+ *   - what the decoder rejects: an entry crossing its block, block offsets out of order;
+ *   - keys not strictly increasing over the whole file (the writer emits a SkipMap; the same demand
+ *     as vbf_compact_merge_*);
+ *   - an index record that is not (last key of its block, start of its block), or index.db not
+ *     exactly one record per block;
+ *   - a block longer than 4096 bytes or of more than 256 entries (the reference's writer produces
+ *     neither: block_manager.rs:121-125).
+ * On a table that passed, find_entry's scan to the end of the file finds a key iff it is in the block
+ * the index step chose (every later key is greater), so both scans are run as binary searches.
+ * An empty table (data_len == 0, nblocks == 0, index_len == 0) opens and holds nothing.  A
+ * zero-length key is an ordinary key (the reference's reader reports UnexpectedEof on one,
+ * fs/mod.rs:355-358). */
+typedef struct vbf_table vbf_table;
+
+/* Borrows the caller's device buffers (exactly vbf_sst_encode_dev's three outputs, or an uploaded
+ * file + its vbf_sst_index_blocks offsets) on the current device; allocates only the side tables.
+ * The buffers must outlive the handle.  Synchronizes `stream` (the validation's verdict). */
+int vbf_table_open_dev(const uint8_t* data, uint64_t data_len, const uint8_t* index, uint64_t index_len,
+                       const uint32_t* blocks, uint64_t nblocks, void* stream, vbf_table** out);
+/* File bytes from the host: uploads them to `device` into buffers the handle owns, parses the block
+ * starts from index.db (vbf_sst_index_blocks), then the same path. */
+int vbf_table_open_host(const uint8_t* data, uint64_t data_len, const uint8_t* index, uint64_t index_len,
+                        int device, vbf_table** out);
+void vbf_table_free(vbf_table* t);
+uint64_t vbf_table_entries(const vbf_table* t);
+uint64_t vbf_table_blocks(const vbf_table* t);
+int vbf_table_device(const vbf_table* t);
+/* smallest = the first entry's key, biggest = the last index record's key (what KeyRange stores,
+ * src/key_range/range.rs:91-147); both empty for an empty table.  *slen / *blen are always written;
+ * NULL buffers make it a size query, a too-small capacity is VBF_EINVAL. */
+int vbf_table_key_range(const vbf_table* t, uint8_t* smallest, uint64_t scap, uint64_t* slen,
+                        uint8_t* biggest, uint64_t bcap, uint64_t* blen);
+
+/* For key j (layout as every entry point: offsets or stride) and tables[0..nsst) in the given order,
+ * DataStore::search_key_in_sstables (src/db/store.rs:579-612):
+ *   found[j]       0 = no table holds it, 1 = the winning entry is live, 2 = it is a tombstone
+ *                  (tombstone byte == 1; any other value is live)
+ *   table_idx[j]   index of the winning table in `tables`, 0xFFFFFFFF when found[j] == 0
+ *   val_offsets[j], created_ms[j]   the winning entry's fields, 0 when found[j] == 0
+ * Per table: get_from_index yields the first index record with key >= key j -- none (the key is
+ * greater than every index key: the reference never reassigns its block_offset, fs/mod.rs:667-710)
+ * skips the table -- and find_entry an equal key in that block.  The fold starts at
+ * default_datetime() (0 ms) and a hit replaces the winner only when its created_at (u64 ms, as
+ * stored) is strictly greater: on a tie the earlier table of `tables` wins, and an entry with
+ * created_at == 0 never wins (found_in_table, store.rs:616-618).
+ * cand (device, n * nsst bytes, vbf_multi_probe_dev's `out`) restricts key j to the tables with
+ * cand[j * nsst + s] != 0; NULL = every table.  A filter built from a table's keys has no false
+ * negatives, so cand only prunes work.  Any output may be NULL.  All tables on one device
+ * (VBF_EINVAL otherwise).  n == 0 is VBF_OK with nothing done; nsst == 0 fills every output
+ * (table_idx too) with zeros.  Queued on `stream` after one synchronisation of it (the table
+ * descriptors' upload). */
+int vbf_table_get_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                      uint32_t nsst, const vbf_table* const* tables, const uint8_t* cand,
+                      uint8_t* found, uint32_t* table_idx, uint32_t* val_offsets, uint64_t* created_ms,
+                      void* stream);
+/* Host keys and host outputs, synchronous.  filters NULL: every table is searched.  filters
+ * non-NULL (nsst device-resident handles on the tables' device, hashed with len_prefix = 1):
+ * vbf_multi_probe_dev with the tables' own key ranges as bounds makes `cand` first --
+ * filter_sstables_by_key_range (src/key_range/range.rs:91-147) then search_key_in_sstables, keys
+ * uploaded once. */
+int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                       uint32_t nsst, const vbf_table* const* tables, const vbf_filter* const* filters,
+                       uint8_t* found, uint32_t* table_idx, uint32_t* val_offsets, uint64_t* created_ms);
 
 #ifdef __cplusplus
 }

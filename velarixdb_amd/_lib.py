@@ -119,6 +119,15 @@ SIGNATURES = {
                                        _vp, _int]),
     "vbf_filter_rebuild_from_sst_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "vbf_filter_rebuild_from_sst_host": (_int, [_vp, _vp, _u64, _vp, _u64, _vp]),
+    "vbf_table_open_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(_vp)]),
+    "vbf_table_open_host": (_int, [_vp, _u64, _vp, _u64, _int, ctypes.POINTER(_vp)]),
+    "vbf_table_free": (None, [_vp]),
+    "vbf_table_entries": (_u64, [_vp]),
+    "vbf_table_blocks": (_u64, [_vp]),
+    "vbf_table_device": (_int, [_vp]),
+    "vbf_table_key_range": (_int, [_vp, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, ctypes.POINTER(_u64)]),
+    "vbf_table_get_dev": (_int, [_vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vbf_table_get_host": (_int, [_vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -171,7 +180,7 @@ def device_count():
 
 PHASES = ("tile_sort", "transpose", "seg_or", "atomic_build", "probe", "sst_walk", "sst_scan", "sst_emit",
           "merge_levels", "fold", "select", "probe_pack", "probe_seg", "probe_out", "enc_tile", "enc_scan",
-          "enc_index", "enc_data")
+          "enc_index", "enc_data", "table_open", "table_get")
 
 
 def profile_read():

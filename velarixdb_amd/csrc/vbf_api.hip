@@ -163,6 +163,9 @@ enum WsSlot {
     kWsSstEnc = 12,
     kWsSstEncIO = 13,
     kWsCompactOut = 14,
+    kWsTableOpen = 15,
+    kWsTableDesc = 16,
+    kWsTableIO = 17,
 };
 struct Workspace {
     int device;
@@ -3227,6 +3230,319 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
     if (index && *index_len) HIP_TRY(hipMemcpyAsync(index, d_idx, *index_len, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     *filter_out = hold.release();
+    return ok();
+}
+
+}  // extern "C"
+
+// ---- point lookups in SST tables ----
+
+// A device-resident SST: the three file buffers (borrowed from the caller, or uploaded into
+// `files`) and the side tables of vbf_table.hip in `side`.  Immutable once opened.
+struct vbf_table {
+    int device = 0;
+    uint64_t entries = 0, nblocks = 0, data_len = 0, index_len = 0;
+    void* files = nullptr;  // open_host: data | index | blocks
+    void* side = nullptr;   // counts | pos | kpos
+    vbf::TableDesc desc{};
+    std::vector<uint8_t> smallest, biggest;  // KeyRange's two keys, read back at open
+    ~vbf_table() {
+        if (hip_forked() || (!files && !side)) return;  // a forked child: the parent's allocations
+        int prev = -1;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(device);
+        if (files) (void)hipFree(files);
+        if (side) (void)hipFree(side);
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+namespace {
+
+// Builds and validates the side tables on the current device; two stream synchronisations (the
+// walk's entry count, then the validation's error word with the key-range positions) and one
+// more for the key-range bytes.
+int table_open(vbf_table& t, const uint8_t* data, uint64_t data_len, const uint8_t* index, uint64_t index_len,
+               const uint32_t* blocks, uint64_t nblocks, hipStream_t s) {
+    t.data_len = data_len;
+    t.index_len = index_len;
+    t.nblocks = nblocks;
+    if (!data_len && !nblocks) {
+        if (index_len)
+            return fail(VBF_EINVAL, "index.db of %llu bytes for an empty data.db", (unsigned long long)index_len);
+        return VBF_OK;
+    }
+    if (data_len > 0xFFFFFFFFull)
+        return fail(VBF_EINVAL, "data.db of %llu bytes: index.db's u32 block starts cannot address it",
+                    (unsigned long long)data_len);
+    vbf::SstArgs w;
+    uint64_t n = 0;
+    int rc = sst_count_pass(data, data_len, blocks, nblocks, s, &w, &n);
+    if (rc) return rc;
+    if (!index) return fail(VBF_EINVAL, "index is NULL");
+    size_t tmpb = 0;
+    HIP_TRY(vbf::scan_u64(nullptr, &tmpb, nullptr, nullptr, nblocks + 1, s));
+    const uint64_t o_pos = align256(nblocks * 4), o_kpos = o_pos + align256(nblocks * 512);
+    HIP_TRY(hipMalloc(&t.side, o_kpos + align256((nblocks + 1) * 8)));
+    char* sb = static_cast<char*>(t.side);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(sb);
+    uint16_t* pos = reinterpret_cast<uint16_t*>(sb + o_pos);
+    uint64_t* kpos = reinterpret_cast<uint64_t*>(sb + o_kpos);
+    const uint64_t o_err = align256((nblocks + 1) * 8), o_tmp = o_err + 256;
+    void* ws = nullptr;
+    if ((rc = get_workspace(s, o_tmp + tmpb, &ws, kWsTableOpen))) return rc;
+    uint64_t* reclen = static_cast<uint64_t*>(ws);
+    uint32_t* err = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + o_err);
+    HIP_TRY(hipMemcpyAsync(counts, w.counts, nblocks * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(reclen + nblocks, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(err, 0, 4, s));
+    HIP_TRY(hipMemsetAsync(err + 1, 0xFF, 8, s));
+    const vbf::TableOpenArgs a{data, data_len, index, index_len, blocks, nblocks, counts, w.pos, w.lmin, w.lmax,
+                               w.ebase, pos, reclen, kpos, err};
+    vbf::phase_begin(vbf::kPhaseTableOpen, s);
+    HIP_TRY(vbf::table_fill(a, s));
+    HIP_TRY(vbf::scan_u64(static_cast<char*>(ws) + o_tmp, &tmpb, reclen, kpos, nblocks + 1, s));
+    HIP_TRY(vbf::table_check(a, s));
+    vbf::phase_end(vbf::kPhaseTableOpen, s);
+    uint32_t ev[3] = {0, 0, 0}, first_len = 0;
+    uint64_t last_rec = 0;
+    HIP_TRY(hipMemcpyAsync(ev, err, 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&last_rec, kpos + nblocks - 1, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&first_len, data, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (ev[0]) {
+        const char* what = (ev[0] & vbf::kTabErrBig)        ? "block longer than 4096 bytes"
+                           : (ev[0] & vbf::kTabErrDense)    ? "more than 256 entries in a block"
+                           : (ev[0] & vbf::kTabErrOrder)    ? "keys not strictly increasing"
+                           : (ev[0] & vbf::kTabErrIndexLen) ? "index.db is not one record per block (wrong length)"
+                                                            : "index.db record differs from its block's last key / start";
+        return fail(VBF_EINVAL, "table rejected at block %u, entry %u: %s", ev[1], ev[2], what);
+    }
+    t.entries = n;
+    t.desc = vbf::TableDesc{data, index, blocks, counts, pos, kpos, nblocks};
+    // smallest = the first entry's key, biggest = the last index record's key (key_range/range.rs)
+    t.smallest.resize(first_len);
+    t.biggest.resize(index_len - last_rec - 8);
+    if (first_len) HIP_TRY(hipMemcpyAsync(t.smallest.data(), data + 4, first_len, hipMemcpyDeviceToHost, s));
+    if (!t.biggest.empty())
+        HIP_TRY(hipMemcpyAsync(t.biggest.data(), index + last_rec + 4, t.biggest.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VBF_OK;
+}
+
+// The argument checks of vbf_table_get_* that need no HIP call.
+int table_get_check(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t nsst,
+                    const vbf_table* const* tables) {
+    int rc = check_keys(keys, offsets, stride, n);
+    if (rc) return rc;
+    if (nsst && !tables) return fail(VBF_EINVAL, "tables is NULL");
+    for (uint32_t i = 0; i < nsst; ++i) {
+        if (!tables[i]) return fail(VBF_EINVAL, "tables[%u] is NULL", i);
+        if (tables[i]->device != tables[0]->device)
+            return fail(VBF_EINVAL, "tables[%u] lives on device %d, tables[0] on %d", i, tables[i]->device,
+                        tables[0]->device);
+    }
+    return VBF_OK;
+}
+
+// Device pointers, on the tables' device: the descriptors go up (one stream synchronisation, their
+// source is pageable), then the lookup is queued on `s`.
+int table_lookup(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t nsst,
+                 const vbf_table* const* tables, const uint8_t* cand, uint8_t* found, uint32_t* table_idx,
+                 uint32_t* val_offsets, uint64_t* created_ms, hipStream_t s) {
+    std::vector<vbf::TableDesc> tab(nsst);
+    for (uint32_t i = 0; i < nsst; ++i) tab[i] = tables[i]->desc;
+    void* ws = nullptr;
+    int rc = get_workspace(s, nsst * sizeof(vbf::TableDesc), &ws, kWsTableDesc);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ws, tab.data(), nsst * sizeof(vbf::TableDesc), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const vbf::TableGetArgs a{keys, offsets, stride, n, nsst, static_cast<const vbf::TableDesc*>(ws), cand,
+                              found, table_idx, val_offsets, created_ms};
+    vbf::phase_begin(vbf::kPhaseTableGet, s);
+    HIP_TRY(vbf::table_get(a, s));
+    vbf::phase_end(vbf::kPhaseTableGet, s);
+    return VBF_OK;
+}
+
+int table_no_memory() { return fail(VBF_ENOMEM, "out of host memory"); }
+
+}  // namespace
+
+extern "C" {
+
+int vbf_table_open_dev(const uint8_t* data, uint64_t data_len, const uint8_t* index, uint64_t index_len,
+                       const uint32_t* blocks, uint64_t nblocks, void* stream, vbf_table** out) {
+    if (!out) return fail(VBF_EINVAL, "out is NULL");
+    *out = nullptr;
+    if ((data_len && !data) || (index_len && !index) || (nblocks && !blocks))
+        return fail(VBF_EINVAL, "NULL argument");
+    FORK_GUARD();
+    try {
+        std::unique_ptr<vbf_table> t(new (std::nothrow) vbf_table());
+        if (!t) return table_no_memory();
+        HIP_TRY(hipGetDevice(&t->device));
+        int rc = table_open(*t, data, data_len, index, index_len, blocks, nblocks, (hipStream_t)stream);
+        if (rc) return rc;
+        *out = t.release();
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+int vbf_table_open_host(const uint8_t* data, uint64_t data_len, const uint8_t* index, uint64_t index_len, int device,
+                        vbf_table** out) {
+    if (!out) return fail(VBF_EINVAL, "out is NULL");
+    *out = nullptr;
+    if ((data_len && !data) || (index_len && !index)) return fail(VBF_EINVAL, "NULL argument");
+    try {
+        std::vector<uint32_t> blk;
+        int rc = parse_index(index, index_len, &blk);
+        if (rc) return rc;
+        std::unique_ptr<vbf_table> t(new (std::nothrow) vbf_table());
+        if (!t) return table_no_memory();
+        DEVICE_SCOPE(device);
+        t->device = device;
+        hipStream_t s;
+        if ((rc = filter_stream(device, &s))) return rc;
+        const uint64_t o_idx = align256(data_len), o_blk = o_idx + align256(index_len);
+        const uint64_t bytes = o_blk + align256(blk.size() * 4);
+        uint8_t* d = nullptr;
+        if (data_len || index_len) {
+            HIP_TRY(hipMalloc(&t->files, bytes));
+            d = static_cast<uint8_t*>(t->files);
+            if (data_len) HIP_TRY(hipMemcpyAsync(d, data, data_len, hipMemcpyHostToDevice, s));
+            if (index_len) HIP_TRY(hipMemcpyAsync(d + o_idx, index, index_len, hipMemcpyHostToDevice, s));
+            if (!blk.empty())
+                HIP_TRY(hipMemcpyAsync(d + o_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));  // pageable sources
+        }
+        rc = table_open(*t, data_len ? d : nullptr, data_len, index_len ? d + o_idx : nullptr, index_len,
+                        blk.empty() ? nullptr : reinterpret_cast<const uint32_t*>(d + o_blk), blk.size(), s);
+        if (rc) return rc;
+        *out = t.release();
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+void vbf_table_free(vbf_table* t) { delete t; }
+uint64_t vbf_table_entries(const vbf_table* t) { return t ? t->entries : 0; }
+uint64_t vbf_table_blocks(const vbf_table* t) { return t ? t->nblocks : 0; }
+int vbf_table_device(const vbf_table* t) { return t ? t->device : VBF_DEVICE_HOST; }
+
+int vbf_table_key_range(const vbf_table* t, uint8_t* smallest, uint64_t scap, uint64_t* slen, uint8_t* biggest,
+                        uint64_t bcap, uint64_t* blen) {
+    if (!t || !slen || !blen) return fail(VBF_EINVAL, "NULL argument");
+    *slen = t->smallest.size();
+    *blen = t->biggest.size();
+    if ((smallest && scap < *slen) || (biggest && bcap < *blen))
+        return fail(VBF_EINVAL, "key buffers hold %llu / %llu < %llu / %llu bytes", (unsigned long long)scap,
+                    (unsigned long long)bcap, (unsigned long long)*slen, (unsigned long long)*blen);
+    if (smallest && *slen) memcpy(smallest, t->smallest.data(), *slen);
+    if (biggest && *blen) memcpy(biggest, t->biggest.data(), *blen);
+    return ok();
+}
+
+int vbf_table_get_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t nsst,
+                      const vbf_table* const* tables, const uint8_t* cand, uint8_t* found, uint32_t* table_idx,
+                      uint32_t* val_offsets, uint64_t* created_ms, void* stream) {
+    int rc = table_get_check(keys, offsets, stride, n, nsst, tables);
+    if (rc) return rc;
+    if (!n) return ok();
+    FORK_GUARD();
+    hipStream_t s = (hipStream_t)stream;
+    if (!nsst) {  // no table: nothing to look up, every output is zero
+        if (found) HIP_TRY(hipMemsetAsync(found, 0, n, s));
+        if (table_idx) HIP_TRY(hipMemsetAsync(table_idx, 0, n * 4, s));
+        if (val_offsets) HIP_TRY(hipMemsetAsync(val_offsets, 0, n * 4, s));
+        if (created_ms) HIP_TRY(hipMemsetAsync(created_ms, 0, n * 8, s));
+        return ok();
+    }
+    try {
+        DEVICE_SCOPE(tables[0]->device);
+        if ((rc = table_lookup(keys, offsets, stride, n, nsst, tables, cand, found, table_idx, val_offsets,
+                               created_ms, s)))
+            return rc;
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t nsst,
+                       const vbf_table* const* tables, const vbf_filter* const* filters, uint8_t* found,
+                       uint32_t* table_idx, uint32_t* val_offsets, uint64_t* created_ms) {
+    int rc = table_get_check(keys, offsets, stride, n, nsst, tables);
+    if (rc) return rc;
+    if (!n) return ok();
+    if (!nsst) {
+        if (found) memset(found, 0, n);
+        if (table_idx) memset(table_idx, 0, n * 4);
+        if (val_offsets) memset(val_offsets, 0, n * 4);
+        if (created_ms) memset(created_ms, 0, n * 8);
+        return ok();
+    }
+    const int device = tables[0]->device;
+    if (filters)
+        for (uint32_t i = 0; i < nsst; ++i) {
+            if (!filters[i]) return fail(VBF_EINVAL, "filters[%u] is NULL", i);
+            if (filters[i]->bits->device != device)
+                return fail(VBF_EINVAL, "filters[%u] lives on device %d, the tables on %d", i,
+                            filters[i]->bits->device, device);
+        }
+    try {
+        DEVICE_SCOPE(device);
+        hipStream_t s;
+        if ((rc = filter_stream(device, &s))) return rc;
+        const uint64_t kbytes = offsets ? offsets[n] - offsets[0] : n * stride;
+        const uint64_t o_off = align256(kbytes), o_cand = o_off + align256(offsets ? (n + 1) * 8 : 0);
+        const uint64_t o_found = o_cand + align256(filters ? n * nsst : 0), o_idx = o_found + align256(n);
+        const uint64_t o_val = o_idx + align256(n * 4), o_cr = o_val + align256(n * 4);
+        void* ws = nullptr;
+        if ((rc = get_workspace(s, o_cr + n * 8, &ws, kWsTableIO))) return rc;
+        uint8_t* d_keys = static_cast<uint8_t*>(ws);
+        uint64_t* d_off = offsets ? reinterpret_cast<uint64_t*>(d_keys + o_off) : nullptr;
+        uint8_t* d_cand = filters ? d_keys + o_cand : nullptr;
+        uint8_t* d_found = found ? d_keys + o_found : nullptr;
+        uint32_t* d_idx = table_idx ? reinterpret_cast<uint32_t*>(d_keys + o_idx) : nullptr;
+        uint32_t* d_val = val_offsets ? reinterpret_cast<uint32_t*>(d_keys + o_val) : nullptr;
+        uint64_t* d_cr = created_ms ? reinterpret_cast<uint64_t*>(d_keys + o_cr) : nullptr;
+        if (kbytes) HIP_TRY(hipMemcpyAsync(d_keys, keys + (offsets ? offsets[0] : 0), kbytes, hipMemcpyHostToDevice, s));
+        if (offsets) {  // rebased to absolute positions in the device copy
+            std::vector<uint64_t> o(offsets, offsets + n + 1);
+            const uint64_t b0 = o[0];
+            for (auto& x : o) x -= b0;
+            HIP_TRY(hipMemcpyAsync(d_off, o.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        if (filters) {  // filter_sstables_by_key_range (range.rs:91-147) with the tables' own key ranges
+            std::vector<uint8_t> bounds;
+            std::vector<uint64_t> boff(1, 0);
+            for (uint32_t i = 0; i < nsst; ++i) {
+                bounds.insert(bounds.end(), tables[i]->smallest.begin(), tables[i]->smallest.end());
+                boff.push_back(bounds.size());
+                bounds.insert(bounds.end(), tables[i]->biggest.begin(), tables[i]->biggest.end());
+                boff.push_back(bounds.size());
+            }
+            bounds.push_back(0);  // never NULL
+            MultiLock lk(filters, nsst);
+            if ((rc = lk.drain())) return rc;
+            if ((rc = multi_probe(d_keys, d_off, stride, n, 1, nsst, filters, bounds.data(), boff.data(), d_cand, s)))
+                return rc;
+        }
+        if ((rc = table_lookup(d_keys, d_off, stride, n, nsst, tables, d_cand, d_found, d_idx, d_val, d_cr, s)))
+            return rc;
+        if (found) HIP_TRY(hipMemcpyAsync(found, d_found, n, hipMemcpyDeviceToHost, s));
+        if (table_idx) HIP_TRY(hipMemcpyAsync(table_idx, d_idx, n * 4, hipMemcpyDeviceToHost, s));
+        if (val_offsets) HIP_TRY(hipMemcpyAsync(val_offsets, d_val, n * 4, hipMemcpyDeviceToHost, s));
+        if (created_ms) HIP_TRY(hipMemcpyAsync(created_ms, d_cr, n * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
     return ok();
 }
 

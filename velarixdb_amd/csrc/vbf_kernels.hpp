@@ -31,7 +31,8 @@ enum Phase { kPhaseTileSort = 0, kPhaseTranspose = 1, kPhaseSegOr = 2, kPhaseAto
              kPhaseProbe = 4, kPhaseSstWalk = 5, kPhaseSstScan = 6, kPhaseSstEmit = 7,
              kPhaseMergeLevels = 8, kPhaseFold = 9, kPhaseSelect = 10, kPhaseProbePack = 11,
              kPhaseProbeSeg = 12, kPhaseProbeOut = 13, kPhaseEncTile = 14, kPhaseEncScan = 15,
-             kPhaseEncIndex = 16, kPhaseEncData = 17, kNumPhases = 18 };
+             kPhaseEncIndex = 16, kPhaseEncData = 17, kPhaseTableOpen = 18, kPhaseTableGet = 19,
+             kNumPhases = 20 };
 void phase_begin(int phase, hipStream_t s);
 void phase_end(int phase, hipStream_t s);
 
@@ -136,6 +137,50 @@ struct SstEncArgs {
 };
 hipError_t sst_enc_segment(const SstEncArgs& a, hipStream_t s);
 hipError_t sst_enc_emit(const SstEncArgs& a, hipStream_t s);
+// Point lookups in SST tables (vbf_table.hip).  A table as the lookup kernel sees it: the three
+// file buffers plus the side tables built at open.
+struct TableDesc {
+    const uint8_t* data;
+    const uint8_t* index;
+    const uint32_t* blocks;   // [nblocks] block starts in data
+    const uint32_t* counts;   // [nblocks] entries per block (<= 256)
+    const uint16_t* pos;      // [nblocks * 256] entry starts within each block
+    const uint64_t* kpos;     // [nblocks + 1] start of index record b in index; [nblocks] = index_len
+    uint64_t nblocks;
+};
+enum : uint32_t { kTabErrBig = 1, kTabErrDense = 2, kTabErrOrder = 4, kTabErrIndexLen = 8, kTabErrIndexRec = 16 };
+struct TableOpenArgs {
+    const uint8_t* data;
+    uint64_t len;
+    const uint8_t* index;
+    uint64_t index_len;
+    const uint32_t* blocks;
+    uint64_t nblocks;
+    const uint32_t* counts;     // the walk pass's outputs (SstArgs)
+    const uint16_t* pos_walk;
+    const uint32_t* lmin;
+    const uint32_t* lmax;
+    const uint64_t* ebase;
+    uint16_t* pos;              // [nblocks * 256] the handle's entry starts (fill pass)
+    uint64_t* reclen;           // [nblocks + 1] bytes of index record b (fill pass); [nblocks] = 0
+    const uint64_t* kpos;       // [nblocks + 1] exclusive scan of reclen (check pass)
+    uint32_t* err;              // [0] kTabErr bits, [1] first bad block, [2] first bad entry
+};
+struct TableGetArgs {
+    const uint8_t* keys;
+    const uint64_t* offsets;  // n + 1 absolute positions, or NULL for `stride`
+    uint64_t stride, n;
+    uint32_t nsst;
+    const TableDesc* tab;     // device, nsst entries, in the caller's table order
+    const uint8_t* cand;      // device n * nsst, or NULL: every table
+    uint8_t* found;           // outputs, each may be NULL
+    uint32_t* table_idx;
+    uint32_t* val_off;
+    uint64_t* created;
+};
+hipError_t table_fill(const TableOpenArgs& a, hipStream_t s);
+hipError_t table_check(const TableOpenArgs& a, hipStream_t s);
+hipError_t table_get(const TableGetArgs& a, hipStream_t s);
 // Batched probe across SSTs (vbf_multi.hip).
 struct MultiSst {
     const uint32_t* words;

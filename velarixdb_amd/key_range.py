@@ -10,6 +10,7 @@ once for all filters.
   candidates(keys, ranges)      -> bool [n, nsst]      range test && filter.contains (:118, :136)
   filter_sstables_many(keys, ranges) -> [[s, ...], ...] per key, in `ranges` order
   contains_all(keys, filters)   -> bool [n, nsst]      filters only, no range test
+  ranges_from_tables(tables, filters) -> [SstRange]     the tables' own key ranges (table.py)
 """
 import ctypes
 from dataclasses import dataclass
@@ -27,6 +28,15 @@ class SstRange:
     smallest_key: bytes
     biggest_key: bytes
     filter: BloomFilter
+
+
+def ranges_from_tables(tables, filters):
+    """One SstRange per opened table (velarixdb_amd.table.Table) with its own smallest / biggest
+    key and its filter: what candidates() needs to pre-filter a get_many over the same tables."""
+    tables, filters = list(tables), list(filters)
+    if len(tables) != len(filters):
+        raise ValueError("one filter per table")
+    return [SstRange(*t.key_range(), f) for t, f in zip(tables, filters)]
 
 
 def _bounds(ranges):
