@@ -467,7 +467,17 @@ int vbf_multi_probe_host_grouped(const uint8_t* keys, const uint64_t* offsets, u
  * `now_ms` for Entry::has_expired (memtable/mem.rs:149-153: now > created + ttl).
  * Output: the merged table's entry ids in key order (out_ids, capacity = all entries), *n_out;
  * and, when upd_ids/upd_time are non-NULL, the keys whose map value changed (an entry id holding
- * the key) with their new time, *n_upd (capacity = all entries).  Synchronous on the stream. */
+ * the key) with their new time, *n_upd (capacity = all entries).  Synchronous on the stream.
+ * Limits and checks: at most 2^31 - 1 entries in all (run_off[nruns] <= 0x7FFFFFFF; the device
+ * selects count in that range), VBF_EINVAL "too many entries" otherwise.  Every argument check
+ * (NULL pointers, run_off not starting at 0 or decreasing, the entry limit, a map without its
+ * arrays) runs on the host before any device work, the same in _dev, _host and
+ * vbf_compact_write_host; no tables (nruns = 0) or only empty ones give VBF_OK with *n_out = 0
+ * and need no device.
+ * Times are i64 and TTLs u64 over their whole range.  has_expired's created + ttl is computed in
+ * u64 and wraps (a negative `created` counts as a large u64): that is this library's and its
+ * oracle's reading of mem.rs:149-153 outside the range of real clocks, not a claim about what
+ * the Rust reference does there (its arithmetic may panic on overflow). */
 int vbf_compact_merge_dev(const uint8_t* keys, const uint64_t* offsets, const int64_t* created_ms,
                           const uint8_t* tombstones, const uint64_t* run_off, uint32_t nruns,
                           const uint8_t* map_keys, const uint64_t* map_off, const int64_t* map_time,
@@ -484,7 +494,8 @@ int vbf_compact_merge_host(const uint8_t* keys, const uint64_t* offsets, const i
                            int device);
 /* ids -> the build's key layout: out_keys packed (capacity out_keys_cap), out_offsets n+1 (from 0),
  * and optionally the per-entry arrays (each needs its input).  *key_bytes (may be NULL) = packed
- * size.  Device pointers; one readback of the size. */
+ * size.  Device pointers; one readback of the size.  n <= 2^31 - 2 (the offsets' scan runs over
+ * n + 1 items), VBF_EINVAL "too many entries" otherwise, checked before any device work. */
 int vbf_gather_entries_dev(const uint8_t* keys, const uint64_t* offsets, const int64_t* created_ms,
                            const uint8_t* tombstones, const uint32_t* val_offsets, const uint32_t* ids,
                            uint64_t n, uint8_t* out_keys, uint64_t out_keys_cap, uint64_t* out_offsets,

@@ -36,7 +36,7 @@ def test_merge_known_answer(ora, golden):
 
 def test_merge_fold_semantics_by_hand(ora):
     """Small cases of sized.rs:207-320 worked out by hand (times in ms, now = 10_000)."""
-    def run(tables, use_ttl=False, ettl=0, tttl=10**9, tmap=None):
+    def run(tables, use_ttl=False, ettl=0, tttl=10**9, tmap=None, now=10_000):
         keys, offs, cr, tb, ro = b"", [0], [], [], [0]
         for t in tables:
             for k, c, d in t:
@@ -48,7 +48,7 @@ def test_merge_fold_semantics_by_hand(ora):
         m = ora.TombstoneMap(tmap or {})
         ids = ora.compact_merge(np.frombuffer(keys, np.uint8), np.asarray(offs, np.uint64),
                                 np.asarray(cr, np.int64), np.asarray(tb, np.uint8), np.asarray(ro, np.uint64),
-                                use_ttl, ettl, tttl, 10_000, m)
+                                use_ttl, ettl, tttl, now, m)
         return ids.tolist(), m.items()
     # newer value wins; ties take the later table
     assert run([[(b"a", 5, 0)], [(b"a", 7, 0)]])[0] == [1]
@@ -66,3 +66,24 @@ def test_merge_fold_semantics_by_hand(ora):
     assert run([[(b"a", 100, 0)], [(b"b", 9_500, 0)]], use_ttl=True, ettl=1_000)[0] == [1]
     # tables[0] is never checked on its own when there is one table
     assert run([[(b"a", 1, 1)]])[0] == [0]
+    # the same at real-epoch times (ms, above bit 40): the low 32 bits of T and T + 2^32 are equal,
+    # so only the high word says which is newer, which is expired and which the map outdates
+    T, H = 1720785462000, 2**32
+    assert run([[(b"a", T + H, 0)], [(b"a", T, 0)]], now=T + H)[0] == [0]
+    assert run([[(b"a", T, 0)], [(b"a", T + H, 0)]], now=T + H)[0] == [1]
+    ids, m = run([[(b"a", T, 0)], [(b"a", T + H, 1)]], now=T + H)
+    assert ids == [1] and m == {b"a": T + H}
+    assert run([[(b"a", T, 0)], [(b"b", T + H, 0)]], use_ttl=True, ettl=1_000, now=T + H)[0] == [1]
+    assert run([[(b"a", T, 0)], [(b"b", T + H, 0)]], use_ttl=True, ettl=H, now=T + H)[0] == [0, 1]  # T + H >= now
+    assert run([[(b"x", 1, 0)], [(b"a", T, 0)]], tmap={b"a": T + H}, now=T + H)[0] == [0]
+    assert run([[(b"x", T, 0)], [(b"a", T + H, 0)]], tmap={b"a": T}, now=T + H)[0] == [1, 0]  # key order: a < x
+    # c == t, the `created > time` edge of tombstone_check: an entry as old as the map's tombstone is
+    # dropped, a value and a tombstone alike, and the map keeps its time; one ms newer is kept
+    ids, m = run([[(b"x", T, 0)], [(b"a", T, 0)]], tmap={b"a": T}, now=T)
+    assert ids == [0] and m == {b"a": T}
+    ids, m = run([[(b"x", T, 0)], [(b"a", T, 1)]], tmap={b"a": T}, now=T)
+    assert ids == [0] and m == {b"a": T}
+    ids, m = run([[(b"x", T, 0)], [(b"a", T + 1, 0)]], tmap={b"a": T}, now=T)
+    assert ids == [1, 0] and m == {b"a": T}
+    ids, m = run([[(b"x", T, 0)], [(b"a", T + 1, 1)]], tmap={b"a": T}, now=T)
+    assert ids == [1, 0] and m == {b"a": T + 1}

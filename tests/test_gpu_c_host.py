@@ -18,7 +18,7 @@ def test_c_host_matches_oracle(vbf, ora, tmp_path):
     from velarixdb_amd.keys import HostBatch
     exe = os.path.join(ROOT, "examples", "c_host")  # built by __graft_entry__.build()
     if not os.path.exists(exe):
-        exe = build.build_examples()
+        build.build_examples()  # one path per example; c_host's is `exe`
     n, L, p = 300_000, 16, 0.01
     keys = np.random.default_rng(5).integers(0, 256, n * L, dtype=np.uint8)
     kf = tmp_path / "keys.bin"

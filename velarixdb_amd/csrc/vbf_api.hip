@@ -2901,6 +2901,27 @@ int vbf_multi_probe_host_grouped(const uint8_t* keys, const uint64_t* offsets, u
 // ---- compaction merge ----
 
 namespace {
+// The merge's argument checks, all on the host and before any device work, shared by the _dev and
+// _host entry points so that both give the same code and message.  hipcub's selects and scans run
+// over the entry count, so it stays below 2^31; that check precedes the NULL checks (a count that
+// large is wrong whatever the pointers are).  *total = run_off[nruns], 0 for no tables.
+int compact_validate(const uint64_t* offsets, const int64_t* created, const uint8_t* tomb, const uint64_t* run_off,
+                     uint32_t nruns, const uint8_t* map_keys, const uint64_t* map_off, const int64_t* map_time,
+                     uint64_t map_n, bool need_out_ids, const uint32_t* out_ids, uint64_t* total) {
+    *total = 0;
+    if (nruns == 0) return VBF_OK;
+    if (!run_off) return fail(VBF_EINVAL, "run_off is NULL");
+    if (run_off[0] != 0) return fail(VBF_EINVAL, "run_off must start at 0");
+    for (uint32_t r = 0; r < nruns; ++r)
+        if (run_off[r + 1] < run_off[r]) return fail(VBF_EINVAL, "run_off not nondecreasing at %u", r);
+    const uint64_t n = run_off[nruns];
+    if (n > 0x7FFFFFFFull) return fail(VBF_EINVAL, "too many entries (%llu > 2^31 - 1)", (unsigned long long)n);
+    if (n && (!offsets || !created || !tomb || (need_out_ids && !out_ids))) return fail(VBF_EINVAL, "NULL argument");
+    if (map_n && (!map_keys || !map_off || !map_time)) return fail(VBF_EINVAL, "map arrays are NULL");
+    *total = n;
+    return VBF_OK;
+}
+
 int compact_merge(const uint8_t* keys, const uint64_t* offsets, const int64_t* created, const uint8_t* tomb,
                   const uint64_t* run_off, uint32_t nruns, const uint8_t* map_keys, const uint64_t* map_off,
                   const int64_t* map_time, uint64_t map_n, int use_ttl, uint64_t entry_ttl_ms, uint64_t tomb_ttl_ms,
@@ -2909,15 +2930,10 @@ int compact_merge(const uint8_t* keys, const uint64_t* offsets, const int64_t* c
     if (!n_out) return fail(VBF_EINVAL, "n_out is NULL");
     *n_out = 0;
     if (n_upd) *n_upd = 0;
-    if (nruns == 0) return VBF_OK;
-    if (!run_off || run_off[0] != 0) return fail(VBF_EINVAL, "run_off must start at 0");
-    for (uint32_t r = 0; r < nruns; ++r)
-        if (run_off[r + 1] < run_off[r]) return fail(VBF_EINVAL, "run_off not nondecreasing at %u", r);
-    const uint64_t total = run_off[nruns];
-    if (total >= 0xFFFFFFFFull) return fail(VBF_EINVAL, "too many entries (%llu)", (unsigned long long)total);
-    if (total && (!keys && offsets == nullptr)) return fail(VBF_EINVAL, "keys/offsets are NULL");
-    if (total && (!offsets || !created || !tomb || !out_ids)) return fail(VBF_EINVAL, "NULL argument");
-    if (map_n && (!map_keys || !map_off || !map_time)) return fail(VBF_EINVAL, "map arrays are NULL");
+    uint64_t total = 0;
+    int rc = compact_validate(offsets, created, tomb, run_off, nruns, map_keys, map_off, map_time, map_n, true,
+                              out_ids, &total);
+    if (rc) return rc;
     if (total == 0) return VBF_OK;
     // merge levels: segment boundaries and per-pair tile starts per level, all uploaded at once
     const uint64_t tile = vbf::compact_tile();
@@ -2956,8 +2972,7 @@ int compact_merge(const uint8_t* keys, const uint64_t* offsets, const int64_t* c
     const uint64_t o_split = o_pq + align256(total * 8), o_misc = o_split + align256(max_tiles * 8);
     const uint64_t o_tmp = o_misc + 256, bytes = o_tmp + t3;
     void* ws = nullptr;
-    int rc = get_workspace(s, bytes, &ws, kWsCompact);
-    if (rc) return rc;
+    if ((rc = get_workspace(s, bytes, &ws, kWsCompact))) return rc;
     char* b = static_cast<char*>(ws);
     uint32_t* ping = reinterpret_cast<uint32_t*>(b);
     uint32_t* pong = reinterpret_cast<uint32_t*>(b + o_pong);
@@ -3015,6 +3030,8 @@ int gather_entries(const uint8_t* keys, const uint64_t* offsets, const int64_t* 
                    const uint32_t* val, const uint32_t* ids, uint64_t n, uint8_t* out_keys, uint64_t out_keys_cap,
                    uint64_t* out_offsets, int64_t* out_created, uint8_t* out_tomb, uint32_t* out_val,
                    uint64_t* key_bytes, hipStream_t s) {
+    // the offsets' scan runs over n + 1 items, which stay below 2^31 (hipcub's count)
+    if (n >= 0x7FFFFFFFull) return fail(VBF_EINVAL, "too many entries (%llu > 2^31 - 2)", (unsigned long long)n);
     if (!out_offsets) return fail(VBF_EINVAL, "out_offsets is NULL");
     if (n && (!offsets || !ids)) return fail(VBF_EINVAL, "NULL argument");
     if ((out_created && !created) || (out_tomb && !tomb) || (out_val && !val))
@@ -3073,15 +3090,14 @@ int vbf_compact_merge_host(const uint8_t* keys, const uint64_t* offsets, const i
     if (!n_out) return fail(VBF_EINVAL, "n_out is NULL");
     *n_out = 0;
     if (n_upd) *n_upd = 0;
-    if (!nruns) return ok();
-    if (!run_off) return fail(VBF_EINVAL, "run_off is NULL");
-    const uint64_t total = run_off[nruns];
-    if (total && (!offsets || !created_ms || !tombstones || !out_ids)) return fail(VBF_EINVAL, "NULL argument");
-    if (map_n && (!map_keys || !map_off || !map_time)) return fail(VBF_EINVAL, "map arrays are NULL");
+    uint64_t total = 0;
+    int rc = compact_validate(offsets, created_ms, tombstones, run_off, nruns, map_keys, map_off, map_time, map_n, true,
+                              out_ids, &total);
+    if (rc) return rc;
+    if (total == 0) return ok();  // no entries: nothing to merge, no device needed
     DEVICE_SCOPE(device);
     hipStream_t s;
-    int rc = filter_stream(device, &s);
-    if (rc) return rc;
+    if ((rc = filter_stream(device, &s))) return rc;
     const uint64_t kb = total ? offsets[total] : 0, mkb = map_n ? map_off[map_n] : 0;
     const uint64_t o_off = align256(kb), o_cr = o_off + align256((total + 1) * 8), o_tb = o_cr + align256(total * 8);
     const uint64_t o_mk = o_tb + align256(total), o_mo = o_mk + align256(mkb), o_mt = o_mo + align256((map_n + 1) * 8);
@@ -3137,14 +3153,13 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
     *n_out = *data_len = *index_len = 0;
     *filter_out = nullptr;
     if (n_upd) *n_upd = 0;
-    if (nruns && !run_off) return fail(VBF_EINVAL, "run_off is NULL");
-    const uint64_t total = nruns ? run_off[nruns] : 0;
-    if (total == 0) return fail(VBF_EINVAL, "empty merge: BloomFilter::new asserts no_of_elements > 0 (bf.rs:67)");
-    if (!offsets || !created_ms || !tombstones) return fail(VBF_EINVAL, "NULL argument");
-    if (map_n && (!map_keys || !map_off || !map_time)) return fail(VBF_EINVAL, "map arrays are NULL");
-    uint32_t m_probe, k_probe;  // bf.rs:63-66: the rate is checked before any work
-    int rc = vbf_size(false_positive, total, &m_probe, &k_probe);
+    uint64_t total = 0;
+    int rc = compact_validate(offsets, created_ms, tombstones, run_off, nruns, map_keys, map_off, map_time, map_n, false,
+                              nullptr, &total);
     if (rc) return rc;
+    if (total == 0) return fail(VBF_EINVAL, "empty merge: BloomFilter::new asserts no_of_elements > 0 (bf.rs:67)");
+    uint32_t m_probe, k_probe;  // bf.rs:63-66: the rate is checked before any work
+    if ((rc = vbf_size(false_positive, total, &m_probe, &k_probe))) return rc;
     DEVICE_SCOPE(device);
     hipStream_t s;
     if ((rc = filter_stream(device, &s))) return rc;

@@ -344,10 +344,15 @@ hipError_t compact_fold(const CompactArgs& a, const uint32_t* order, const uint6
     return hipGetLastError();
 }
 
+// hipcub counts items in 64 bits; the entry points keep every count below 2^31 (vbf.h), and a
+// larger one is an error here, never a truncated or negative count.
+constexpr uint64_t kMaxItems = 0x7FFFFFFFull;
+
 template <class T>
 static hipError_t select_flagged(void* tmp, size_t* bytes, const T* in, const uint8_t* flags, T* out,
                                  uint64_t* nsel, uint64_t n, hipStream_t s) {
-    return hipcub::DeviceSelect::Flagged(tmp, *bytes, in, flags, out, nsel, (int)n, s);
+    if (n > kMaxItems) return hipErrorInvalidValue;
+    return hipcub::DeviceSelect::Flagged(tmp, *bytes, in, flags, out, nsel, (int64_t)n, s);
 }
 
 hipError_t select_u32(void* tmp, size_t* bytes, const uint32_t* in, const uint8_t* flags, uint32_t* out,
@@ -384,7 +389,8 @@ hipError_t gather_lens(const uint64_t* offsets, const uint32_t* ids, uint64_t n,
 }
 
 hipError_t scan_u64(void* tmp, size_t* bytes, const uint64_t* in, uint64_t* out, uint64_t n, hipStream_t s) {
-    return hipcub::DeviceScan::ExclusiveSum(tmp, *bytes, in, out, (int)n, s);
+    if (n > kMaxItems) return hipErrorInvalidValue;
+    return hipcub::DeviceScan::ExclusiveSum(tmp, *bytes, in, out, (int64_t)n, s);
 }
 
 hipError_t gather(const GatherArgs& g, hipStream_t s) {
