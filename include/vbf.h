@@ -36,6 +36,7 @@
  *   Table::get                         src/sst/table.rs:184-193    -> vbf_table_get_* (block step)
  *   DataFileNode::find_entry           src/fs/mod.rs:334-389       -> vbf_table_get_* (block step)
  *   DataStore::search_key_in_sstables  src/db/store.rs:579-612     -> vbf_table_open_* + vbf_table_get_*
+ *   DataStore::seek (a stub there)     src/range/range_iterator.rs:47-60 -> vbf_table_scan_* (the key side)
  *
  * Key batches.  `keys` holds the key bytes back to back.  When `offsets` is non-NULL it has
  * n+1 nondecreasing entries and key j is keys[offsets[j] .. offsets[j+1]) (positions are
@@ -80,7 +81,8 @@ int vbf_device_count(int* count);
  * 5 data.db walk, 6 data.db scan, 7 data.db emit, 8 compaction merge levels, 9 fold, 10 select,
  * 11 partitioned-probe pack, 12 probe segment test, 13 probe answers, 14 SST-encode tile tables,
  * 15 encode table scan + block count, 16 index.db emit, 17 data.db emit, 18 table open (side
- * tables + validation), 19 table get.
+ * tables + validation), 19 table get, 20 table scan bounds + rank (with their scans), 21 table scan
+ * emit + key copy.
  * vbf_profile_read synchronizes, returns per-phase summed ms and launch counts, and resets. */
 int vbf_profile_enable(int on);
 int vbf_profile_read(double* ms, uint64_t* launches, int nphases);
@@ -531,8 +533,8 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
  * looked up in every table in one launch; only the value-log read is left to the host.
  *
  * A vbf_table holds data.db, index.db and the block starts on the device plus side tables built at
- * open (every block's entry starts and count, the start of every index record).  Open validates the
- * files once; VBF_EINVAL, with the first offending block or entry in vbf_last_error(), for
+ * open (every block's entry starts and count, the entries before every block, the start of every
+ * index record).  Open validates the files once; VBF_EINVAL, with the first offending block or entry in vbf_last_error(), for
  *   - what the decoder rejects: an entry crossing its block, block offsets out of order;
  *   - keys not strictly increasing over the whole file (the writer emits a SkipMap; the same demand
  *     as vbf_compact_merge_*);
@@ -596,6 +598,63 @@ int vbf_table_get_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t str
 int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
                        uint32_t nsst, const vbf_table* const* tables, const vbf_filter* const* filters,
                        uint8_t* found, uint32_t* table_idx, uint32_t* val_offsets, uint64_t* created_ms);
+
+/* ---- batched range scans over open tables ----
+ * The key side of DataStore::seek(start, end) (src/range/range_iterator.rs:47-60, a stub in the
+ * reference; Range Query is on its TODO list): the merged, newest-wins entries of every table whose
+ * key lies in the range -- what a `seek` binding hands to RangeIterator.keys before it fetches the
+ * values from the value log.  The scan has no semantics of its own: for range r and
+ * tables[0..nsst) in the given order, let U_r be the distinct keys k held by some table with
+ * lo_r <= k <= hi_r (Rust's `Ord for [u8]`, both ends inclusive as KeyRange tests,
+ * src/key_range/range.rs:101-113).  The scan of r lists, in ascending key order, every k of U_r
+ * for which vbf_table_get_* over the same tables in the same order reports found != 0, with exactly
+ * that call's table_idx, val_offsets and created_ms.  So, as there: the strictly newest created_at
+ * wins, on a tie the earlier table of `tables`, an entry with created_at == 0 never wins (a key
+ * whose copies are all at time 0 is absent), a tombstone is byte == 1.
+ * flags (an unknown bit is VBF_EINVAL):
+ *   VBF_SCAN_KEEP_TOMBSTONES  keys whose winner is a tombstone are listed with tombstones[i] = 1;
+ *                             without it they are omitted.  Either way a newer tombstone hides an
+ *                             older live entry of another table.
+ *   VBF_SCAN_END_EXCLUSIVE    lo_r <= k < hi_r.
+ * lo_r > hi_r is an empty range, not an error; so is lo_r == hi_r with END_EXCLUSIVE.  A zero-length
+ * lo_r starts at the first key; a zero-length key is an ordinary key.
+ * bounds / bounds_off: vbf_multi_probe_*'s layout -- lo_r = bounds[bounds_off[2r] ..
+ * bounds_off[2r+1]), hi_r = bounds[bounds_off[2r+1] .. bounds_off[2r+2]); 2 * nranges + 1
+ * nondecreasing entries, bounds_off[0] need not be 0 -- on the tables' device in _dev, in host
+ * memory in _host.
+ * Outputs (device arrays in _dev, host arrays in _host): output i belongs to range r when
+ * range_off[r] <= i < range_off[r+1] (nranges + 1 entries, from 0, not subject to entries_cap); its
+ * key is keys[key_off[i] .. key_off[i+1]) (key_off: n_out + 1 entries, from 0, so entries_cap + 1
+ * slots); table_idx / val_offsets / created_ms / tombstones hold entries_cap items.  Every output
+ * array may be NULL; all of them NULL is the size query.  *n_out (listed entries) and *key_bytes
+ * are always written; a capacity that is too small (entries_cap < *n_out with a per-entry array
+ * given, keys_cap < *key_bytes with keys given) is VBF_EINVAL with the sizes written and nothing
+ * written to the outputs (the encoder's convention).
+ * nranges == 0 is VBF_OK with zero sizes and no device work (_dev then writes no output; _host
+ * writes range_off[0] = key_off[0] = 0).  nsst == 0, or only empty tables, gives empty ranges.
+ * All tables on one device.  Every argument check (NULL pointers, unknown flags, a table on another
+ * device; in _host also a descending bounds_off, which _dev reports after its first pass) runs on
+ * the host before any HIP call.  The candidate entries -- the sum, over ranges and tables, of the
+ * table's entries inside the range -- are limited to 2^31 - 1, VBF_EINVAL "too many entries"
+ * beyond, like the compaction merge.
+ * Work is O(candidates x nsst x log(entries per table)) key comparisons: every candidate searches
+ * its key in every other table.  That suits short and medium ranges; it is not a merge-path scan.
+ * Workspace (cached per stream like every other): 40 bytes per candidate + 24 per (range, table)
+ * pair, plus the scans' scratch.
+ * _dev synchronises `stream` three times (the table descriptors' upload, the candidate total, the
+ * two sizes); the output passes stay queued on it.  _host is synchronous. */
+#define VBF_SCAN_KEEP_TOMBSTONES 1u
+#define VBF_SCAN_END_EXCLUSIVE 2u
+int vbf_table_scan_dev(const uint8_t* bounds, const uint64_t* bounds_off, uint64_t nranges, uint32_t nsst,
+                       const vbf_table* const* tables, uint32_t flags, uint64_t* range_off, uint8_t* keys,
+                       uint64_t keys_cap, uint64_t* key_off, uint32_t* table_idx, uint32_t* val_offsets,
+                       uint64_t* created_ms, uint8_t* tombstones, uint64_t entries_cap, uint64_t* n_out,
+                       uint64_t* key_bytes, void* stream);
+int vbf_table_scan_host(const uint8_t* bounds, const uint64_t* bounds_off, uint64_t nranges, uint32_t nsst,
+                        const vbf_table* const* tables, uint32_t flags, uint64_t* range_off, uint8_t* keys,
+                        uint64_t keys_cap, uint64_t* key_off, uint32_t* table_idx, uint32_t* val_offsets,
+                        uint64_t* created_ms, uint8_t* tombstones, uint64_t entries_cap, uint64_t* n_out,
+                        uint64_t* key_bytes);
 
 #ifdef __cplusplus
 }

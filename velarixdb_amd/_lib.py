@@ -25,6 +25,7 @@ VBF_BUILD_AUTO = 0
 VBF_BUILD_ATOMIC = 1
 VBF_BUILD_PARTITIONED = 2
 VBF_BUILD_FRESH = 0x100  # OR into a build strategy: BloomFilter::new fused with the build (vbf.h)
+VBF_SCAN_KEEP_TOMBSTONES, VBF_SCAN_END_EXCLUSIVE = 1, 2  # vbf_table_scan_* flags
 
 _u8p = ctypes.c_void_p  # raw pointers (host or device) travel as integers
 _u64 = ctypes.c_uint64
@@ -128,6 +129,10 @@ SIGNATURES = {
     "vbf_table_key_range": (_int, [_vp, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, ctypes.POINTER(_u64)]),
     "vbf_table_get_dev": (_int, [_vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vbf_table_get_host": (_int, [_vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vbf_table_scan_dev": (_int, [_vp, _vp, _u64, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64,
+                                   ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp]),
+    "vbf_table_scan_host": (_int, [_vp, _vp, _u64, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64,
+                                    ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
 }
 
 
@@ -180,7 +185,7 @@ def device_count():
 
 PHASES = ("tile_sort", "transpose", "seg_or", "atomic_build", "probe", "sst_walk", "sst_scan", "sst_emit",
           "merge_levels", "fold", "select", "probe_pack", "probe_seg", "probe_out", "enc_tile", "enc_scan",
-          "enc_index", "enc_data", "table_open", "table_get")
+          "enc_index", "enc_data", "table_open", "table_get", "scan_rank", "scan_emit")
 
 
 def profile_read():

@@ -166,6 +166,9 @@ enum WsSlot {
     kWsTableOpen = 15,
     kWsTableDesc = 16,
     kWsTableIO = 17,
+    kWsTableScanPairs = 18,
+    kWsTableScan = 19,
+    kWsTableScanIO = 20,
 };
 struct Workspace {
     int device;
@@ -3258,7 +3261,7 @@ struct vbf_table {
     int device = 0;
     uint64_t entries = 0, nblocks = 0, data_len = 0, index_len = 0;
     void* files = nullptr;  // open_host: data | index | blocks
-    void* side = nullptr;   // counts | pos | kpos
+    void* side = nullptr;   // counts | pos | kpos | ebase
     vbf::TableDesc desc{};
     std::vector<uint8_t> smallest, biggest;  // KeyRange's two keys, read back at open
     ~vbf_table() {
@@ -3298,17 +3301,20 @@ int table_open(vbf_table& t, const uint8_t* data, uint64_t data_len, const uint8
     size_t tmpb = 0;
     HIP_TRY(vbf::scan_u64(nullptr, &tmpb, nullptr, nullptr, nblocks + 1, s));
     const uint64_t o_pos = align256(nblocks * 4), o_kpos = o_pos + align256(nblocks * 512);
-    HIP_TRY(hipMalloc(&t.side, o_kpos + align256((nblocks + 1) * 8)));
+    const uint64_t o_ebase = o_kpos + align256((nblocks + 1) * 8);
+    HIP_TRY(hipMalloc(&t.side, o_ebase + align256((nblocks + 1) * 8)));
     char* sb = static_cast<char*>(t.side);
     uint32_t* counts = reinterpret_cast<uint32_t*>(sb);
     uint16_t* pos = reinterpret_cast<uint16_t*>(sb + o_pos);
     uint64_t* kpos = reinterpret_cast<uint64_t*>(sb + o_kpos);
+    uint64_t* ebase = reinterpret_cast<uint64_t*>(sb + o_ebase);
     const uint64_t o_err = align256((nblocks + 1) * 8), o_tmp = o_err + 256;
     void* ws = nullptr;
     if ((rc = get_workspace(s, o_tmp + tmpb, &ws, kWsTableOpen))) return rc;
     uint64_t* reclen = static_cast<uint64_t*>(ws);
     uint32_t* err = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + o_err);
     HIP_TRY(hipMemcpyAsync(counts, w.counts, nblocks * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ebase, w.ebase, (nblocks + 1) * 8, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(reclen + nblocks, 0, 8, s));
     HIP_TRY(hipMemsetAsync(err, 0, 4, s));
     HIP_TRY(hipMemsetAsync(err + 1, 0xFF, 8, s));
@@ -3334,7 +3340,7 @@ int table_open(vbf_table& t, const uint8_t* data, uint64_t data_len, const uint8
         return fail(VBF_EINVAL, "table rejected at block %u, entry %u: %s", ev[1], ev[2], what);
     }
     t.entries = n;
-    t.desc = vbf::TableDesc{data, index, blocks, counts, pos, kpos, nblocks};
+    t.desc = vbf::TableDesc{data, index, blocks, counts, pos, kpos, ebase, nblocks};
     // smallest = the first entry's key, biggest = the last index record's key (key_range/range.rs)
     t.smallest.resize(first_len);
     t.biggest.resize(index_len - last_rec - 8);
@@ -3360,11 +3366,9 @@ int table_get_check(const uint8_t* keys, const uint64_t* offsets, uint64_t strid
     return VBF_OK;
 }
 
-// Device pointers, on the tables' device: the descriptors go up (one stream synchronisation, their
-// source is pageable), then the lookup is queued on `s`.
-int table_lookup(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t nsst,
-                 const vbf_table* const* tables, const uint8_t* cand, uint8_t* found, uint32_t* table_idx,
-                 uint32_t* val_offsets, uint64_t* created_ms, hipStream_t s) {
+// The tables' descriptors in the caller's order, uploaded to the tables' device: one stream
+// synchronisation (their source is pageable).
+int table_descs(uint32_t nsst, const vbf_table* const* tables, hipStream_t s, const vbf::TableDesc** out) {
     std::vector<vbf::TableDesc> tab(nsst);
     for (uint32_t i = 0; i < nsst; ++i) tab[i] = tables[i]->desc;
     void* ws = nullptr;
@@ -3372,8 +3376,18 @@ int table_lookup(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, 
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(ws, tab.data(), nsst * sizeof(vbf::TableDesc), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const vbf::TableGetArgs a{keys, offsets, stride, n, nsst, static_cast<const vbf::TableDesc*>(ws), cand,
-                              found, table_idx, val_offsets, created_ms};
+    *out = static_cast<const vbf::TableDesc*>(ws);
+    return VBF_OK;
+}
+
+// Device pointers, on the tables' device: the descriptors go up, then the lookup is queued on `s`.
+int table_lookup(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t nsst,
+                 const vbf_table* const* tables, const uint8_t* cand, uint8_t* found, uint32_t* table_idx,
+                 uint32_t* val_offsets, uint64_t* created_ms, hipStream_t s) {
+    const vbf::TableDesc* tab = nullptr;
+    int rc = table_descs(nsst, tables, s, &tab);
+    if (rc) return rc;
+    const vbf::TableGetArgs a{keys, offsets, stride, n, nsst, tab, cand, found, table_idx, val_offsets, created_ms};
     vbf::phase_begin(vbf::kPhaseTableGet, s);
     HIP_TRY(vbf::table_get(a, s));
     vbf::phase_end(vbf::kPhaseTableGet, s);
@@ -3554,6 +3568,252 @@ int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t st
         if (table_idx) HIP_TRY(hipMemcpyAsync(table_idx, d_idx, n * 4, hipMemcpyDeviceToHost, s));
         if (val_offsets) HIP_TRY(hipMemcpyAsync(val_offsets, d_val, n * 4, hipMemcpyDeviceToHost, s));
         if (created_ms) HIP_TRY(hipMemcpyAsync(created_ms, d_cr, n * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+}  // extern "C"
+
+// ---- batched range scans over open tables (DataStore::seek's key side) ----
+
+namespace {
+
+// The argument checks of vbf_table_scan_* that need no HIP call.
+int table_scan_check(const uint8_t* bounds, const uint64_t* bounds_off, uint64_t nranges, uint32_t nsst,
+                     const vbf_table* const* tables, uint32_t flags, uint64_t* n_out, uint64_t* key_bytes) {
+    if (!n_out || !key_bytes) return fail(VBF_EINVAL, "n_out or key_bytes is NULL");
+    *n_out = 0;
+    *key_bytes = 0;
+    if (flags & ~(uint32_t)(VBF_SCAN_KEEP_TOMBSTONES | VBF_SCAN_END_EXCLUSIVE))
+        return fail(VBF_EINVAL, "unknown flag bits 0x%x", flags);
+    if (nsst && !tables) return fail(VBF_EINVAL, "tables is NULL");
+    for (uint32_t i = 0; i < nsst; ++i) {
+        if (!tables[i]) return fail(VBF_EINVAL, "tables[%u] is NULL", i);
+        if (tables[i]->device != tables[0]->device)
+            return fail(VBF_EINVAL, "tables[%u] lives on device %d, tables[0] on %d", i, tables[i]->device,
+                        tables[0]->device);
+    }
+    if (nranges && !bounds_off) return fail(VBF_EINVAL, "bounds_off is NULL");
+    if (nranges && !bounds) return fail(VBF_EINVAL, "bounds is NULL");
+    // the (range, table) pairs are scanned like the candidates: below 2^31 items
+    if (nsst && nranges > 0x7FFFFFFEull / nsst)
+        return fail(VBF_EINVAL, "too many entries: %llu ranges x %u tables", (unsigned long long)nranges, nsst);
+    return VBF_OK;
+}
+
+struct ScanOut {
+    uint64_t* range_off;
+    uint8_t* keys;
+    uint64_t* key_off;
+    uint32_t* table_idx;
+    uint32_t* val_offsets;
+    uint64_t* created_ms;
+    uint8_t* tombstones;
+    bool per_entry() const { return key_off || table_idx || val_offsets || created_ms || tombstones; }
+    bool any() const { return range_off || keys || per_entry(); }
+};
+
+// The capacity rule of the sizing protocol (the encoder's convention): too small is VBF_EINVAL
+// with the sizes written and no output touched.
+int table_scan_caps(const ScanOut& o, uint64_t entries_cap, uint64_t keys_cap, uint64_t n_out, uint64_t key_bytes) {
+    if (o.per_entry() && entries_cap < n_out)
+        return fail(VBF_EINVAL, "entries_cap %llu < %llu listed entries", (unsigned long long)entries_cap,
+                    (unsigned long long)n_out);
+    if (o.keys && keys_cap < key_bytes)
+        return fail(VBF_EINVAL, "keys_cap %llu < %llu key bytes", (unsigned long long)keys_cap,
+                    (unsigned long long)key_bytes);
+    return VBF_OK;
+}
+
+// Bounds pass, rank pass and the two scans on the tables' device (bounds / bounds_off there):
+// everything the sizes need.  Three stream synchronisations: the descriptors' upload, the candidate
+// total, then *n_out and *key_bytes.  `a` comes back ready for table_scan_fill.
+// Workspace: 40 bytes per candidate (slot -> table and entry start, listed flag and key length as
+// u64 for scan_u64, their two scans) and 24 per (range, table) pair, plus the scans' scratch.
+int table_scan_sizes(const uint8_t* bounds, const uint64_t* bounds_off, uint64_t nranges, uint32_t nsst,
+                     const vbf_table* const* tables, uint32_t flags, hipStream_t s, vbf::TableScanArgs* a,
+                     uint64_t* n_out, uint64_t* key_bytes) {
+    *a = vbf::TableScanArgs{};
+    a->bounds = bounds;
+    a->bounds_off = bounds_off;
+    a->nranges = nranges;
+    a->nsst = nsst;
+    a->flags = flags;
+    int rc = table_descs(nsst, tables, s, &a->tab);
+    if (rc) return rc;
+    const uint64_t P = nranges * nsst;
+    size_t tmpb = 0;
+    HIP_TRY(vbf::scan_u64(nullptr, &tmpb, nullptr, nullptr, P + 1, s));
+    const uint64_t o_cnt = align256(P * 8), o_cbase = o_cnt + align256((P + 1) * 8);
+    const uint64_t o_err = o_cbase + align256((P + 1) * 8), o_tmp = o_err + 256;
+    void* ws = nullptr;
+    if ((rc = get_workspace(s, o_tmp + tmpb, &ws, kWsTableScanPairs))) return rc;
+    char* pb = static_cast<char*>(ws);
+    a->first = reinterpret_cast<uint64_t*>(pb);
+    a->cnt = reinterpret_cast<uint64_t*>(pb + o_cnt);
+    uint64_t* cbase = reinterpret_cast<uint64_t*>(pb + o_cbase);
+    a->cbase = cbase;
+    a->err = reinterpret_cast<uint32_t*>(pb + o_err);
+    HIP_TRY(hipMemsetAsync(a->cnt + P, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(a->err, 0, 4, s));
+    vbf::phase_begin(vbf::kPhaseScanRank, s);
+    HIP_TRY(vbf::table_scan_bounds(*a, s));
+    HIP_TRY(vbf::scan_u64(pb + o_tmp, &tmpb, a->cnt, cbase, P + 1, s));
+    vbf::phase_end(vbf::kPhaseScanRank, s);
+    uint64_t total = 0;
+    uint32_t ev = 0;
+    HIP_TRY(hipMemcpyAsync(&total, cbase + P, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&ev, a->err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (ev & vbf::kScanErrBounds) return fail(VBF_EINVAL, "bounds_off is not nondecreasing");
+    if (total > 0x7FFFFFFFull)
+        return fail(VBF_EINVAL, "too many entries: %llu candidates in the ranges (limit 2^31 - 1)",
+                    (unsigned long long)total);
+    a->total = total;
+    size_t tmpc = 0;
+    HIP_TRY(vbf::scan_u64(nullptr, &tmpc, nullptr, nullptr, total + 1, s));
+    const uint64_t q_pos = align256(total * 4), q_keep = q_pos + align256(total * 4);
+    const uint64_t q_len = q_keep + (total + 1) * 8, q_opos = align256(q_len + (total + 1) * 8);
+    const uint64_t q_kofs = q_opos + align256((total + 1) * 8), q_tmp = q_kofs + align256((total + 1) * 8);
+    if ((rc = get_workspace(s, q_tmp + tmpc, &ws, kWsTableScan))) return rc;
+    char* cb = static_cast<char*>(ws);
+    a->m_table = reinterpret_cast<uint32_t*>(cb);
+    a->m_pos = reinterpret_cast<uint32_t*>(cb + q_pos);
+    a->m_keep = reinterpret_cast<uint64_t*>(cb + q_keep);
+    a->m_len = reinterpret_cast<uint64_t*>(cb + q_len);
+    uint64_t* opos = reinterpret_cast<uint64_t*>(cb + q_opos);
+    uint64_t* kofs = reinterpret_cast<uint64_t*>(cb + q_kofs);
+    a->opos = opos;
+    a->kofs = kofs;
+    HIP_TRY(hipMemsetAsync(a->m_keep, 0, (total + 1) * 16, s));  // m_keep | m_len
+    vbf::phase_begin(vbf::kPhaseScanRank, s);
+    HIP_TRY(vbf::table_scan_rank(*a, s));
+    HIP_TRY(vbf::scan_u64(cb + q_tmp, &tmpc, a->m_keep, opos, total + 1, s));
+    HIP_TRY(vbf::scan_u64(cb + q_tmp, &tmpc, a->m_len, kofs, total + 1, s));
+    vbf::phase_end(vbf::kPhaseScanRank, s);
+    HIP_TRY(hipMemcpyAsync(n_out, opos + total, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(key_bytes, kofs + total, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&ev, a->err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (ev & vbf::kScanErrRank) {
+        *n_out = *key_bytes = 0;
+        return fail(VBF_EINVAL, "a merged rank fell outside its range: the tables' buffers changed since open");
+    }
+    return VBF_OK;
+}
+
+// The output passes, queued on `s` (device pointers; each may be NULL).
+int table_scan_fill(vbf::TableScanArgs a, const ScanOut& o, hipStream_t s) {
+    a.range_off = o.range_off;
+    a.keys = o.keys;
+    a.key_off = o.key_off;
+    a.table_idx = o.table_idx;
+    a.val_off = o.val_offsets;
+    a.created = o.created_ms;
+    a.tomb = o.tombstones;
+    vbf::phase_begin(vbf::kPhaseScanEmit, s);
+    HIP_TRY(vbf::table_scan_emit(a, s));
+    HIP_TRY(vbf::table_scan_keys(a, s));
+    vbf::phase_end(vbf::kPhaseScanEmit, s);
+    return VBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbf_table_scan_dev(const uint8_t* bounds, const uint64_t* bounds_off, uint64_t nranges, uint32_t nsst,
+                       const vbf_table* const* tables, uint32_t flags, uint64_t* range_off, uint8_t* keys,
+                       uint64_t keys_cap, uint64_t* key_off, uint32_t* table_idx, uint32_t* val_offsets,
+                       uint64_t* created_ms, uint8_t* tombstones, uint64_t entries_cap, uint64_t* n_out,
+                       uint64_t* key_bytes, void* stream) {
+    int rc = table_scan_check(bounds, bounds_off, nranges, nsst, tables, flags, n_out, key_bytes);
+    if (rc) return rc;
+    if (!nranges) return ok();
+    FORK_GUARD();
+    hipStream_t s = (hipStream_t)stream;
+    const ScanOut o{range_off, keys, key_off, table_idx, val_offsets, created_ms, tombstones};
+    if (!nsst) {  // no table: every range is empty
+        if (range_off) HIP_TRY(hipMemsetAsync(range_off, 0, (nranges + 1) * 8, s));
+        if (key_off) HIP_TRY(hipMemsetAsync(key_off, 0, 8, s));
+        return ok();
+    }
+    try {
+        DEVICE_SCOPE(tables[0]->device);
+        vbf::TableScanArgs a;
+        if ((rc = table_scan_sizes(bounds, bounds_off, nranges, nsst, tables, flags, s, &a, n_out, key_bytes)))
+            return rc;
+        if ((rc = table_scan_caps(o, entries_cap, keys_cap, *n_out, *key_bytes))) return rc;
+        if (o.any() && (rc = table_scan_fill(a, o, s))) return rc;
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+int vbf_table_scan_host(const uint8_t* bounds, const uint64_t* bounds_off, uint64_t nranges, uint32_t nsst,
+                        const vbf_table* const* tables, uint32_t flags, uint64_t* range_off, uint8_t* keys,
+                        uint64_t keys_cap, uint64_t* key_off, uint32_t* table_idx, uint32_t* val_offsets,
+                        uint64_t* created_ms, uint8_t* tombstones, uint64_t entries_cap, uint64_t* n_out,
+                        uint64_t* key_bytes) {
+    int rc = table_scan_check(bounds, bounds_off, nranges, nsst, tables, flags, n_out, key_bytes);
+    if (rc) return rc;
+    for (uint64_t i = 0; i < 2 * nranges; ++i)
+        if (bounds_off[i] > bounds_off[i + 1])
+            return fail(VBF_EINVAL, "bounds_off decreases at entry %llu", (unsigned long long)(i + 1));
+    const ScanOut o{range_off, keys, key_off, table_idx, val_offsets, created_ms, tombstones};
+    if (!nranges || !nsst) {  // nothing to scan: every range is empty, no device work
+        if (range_off) memset(range_off, 0, (nranges + 1) * 8);
+        if (key_off) key_off[0] = 0;
+        return ok();
+    }
+    const int device = tables[0]->device;
+    try {
+        DEVICE_SCOPE(device);
+        hipStream_t s;
+        if ((rc = filter_stream(device, &s))) return rc;
+        // bounds and their offsets, rebased to positions in the device copy
+        const uint64_t b0 = bounds_off[0], bbytes = bounds_off[2 * nranges] - b0;
+        const uint64_t o_boff = align256(bbytes);
+        void* ws = nullptr;
+        if ((rc = get_workspace(s, o_boff + (2 * nranges + 1) * 8, &ws, kWsTableScanIO))) return rc;
+        uint8_t* d_bounds = static_cast<uint8_t*>(ws);
+        uint64_t* d_boff = reinterpret_cast<uint64_t*>(d_bounds + o_boff);
+        std::vector<uint64_t> boff(bounds_off, bounds_off + 2 * nranges + 1);
+        for (auto& x : boff) x -= b0;
+        if (bbytes) HIP_TRY(hipMemcpyAsync(d_bounds, bounds + b0, bbytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_boff, boff.data(), boff.size() * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));  // pageable sources
+        vbf::TableScanArgs a;
+        if ((rc = table_scan_sizes(d_bounds, d_boff, nranges, nsst, tables, flags, s, &a, n_out, key_bytes)))
+            return rc;
+        if ((rc = table_scan_caps(o, entries_cap, keys_cap, *n_out, *key_bytes))) return rc;
+        if (!o.any()) return ok();
+        // the outputs' device staging; the bounds (same slot) were consumed before the sizes came back
+        const uint64_t n = *n_out, kb = *key_bytes;
+        const uint64_t o_koff = align256((nranges + 1) * 8), o_cr = o_koff + align256((n + 1) * 8);
+        const uint64_t o_idx = o_cr + align256(n * 8), o_val = o_idx + align256(n * 4);
+        const uint64_t o_tomb = o_val + align256(n * 4), o_keys = o_tomb + align256(n);
+        if ((rc = get_workspace(s, o_keys + kb, &ws, kWsTableScanIO))) return rc;
+        char* ob = static_cast<char*>(ws);
+        const ScanOut d{range_off ? reinterpret_cast<uint64_t*>(ob) : nullptr,
+                        keys ? reinterpret_cast<uint8_t*>(ob + o_keys) : nullptr,
+                        key_off ? reinterpret_cast<uint64_t*>(ob + o_koff) : nullptr,
+                        table_idx ? reinterpret_cast<uint32_t*>(ob + o_idx) : nullptr,
+                        val_offsets ? reinterpret_cast<uint32_t*>(ob + o_val) : nullptr,
+                        created_ms ? reinterpret_cast<uint64_t*>(ob + o_cr) : nullptr,
+                        tombstones ? reinterpret_cast<uint8_t*>(ob + o_tomb) : nullptr};
+        if ((rc = table_scan_fill(a, d, s))) return rc;
+        if (range_off) HIP_TRY(hipMemcpyAsync(range_off, d.range_off, (nranges + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (key_off) HIP_TRY(hipMemcpyAsync(key_off, d.key_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (keys && kb) HIP_TRY(hipMemcpyAsync(keys, d.keys, kb, hipMemcpyDeviceToHost, s));
+        if (table_idx && n) HIP_TRY(hipMemcpyAsync(table_idx, d.table_idx, n * 4, hipMemcpyDeviceToHost, s));
+        if (val_offsets && n) HIP_TRY(hipMemcpyAsync(val_offsets, d.val_offsets, n * 4, hipMemcpyDeviceToHost, s));
+        if (created_ms && n) HIP_TRY(hipMemcpyAsync(created_ms, d.created_ms, n * 8, hipMemcpyDeviceToHost, s));
+        if (tombstones && n) HIP_TRY(hipMemcpyAsync(tombstones, d.tombstones, n, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     } catch (const std::bad_alloc&) {
         return table_no_memory();

@@ -32,7 +32,7 @@ enum Phase { kPhaseTileSort = 0, kPhaseTranspose = 1, kPhaseSegOr = 2, kPhaseAto
              kPhaseMergeLevels = 8, kPhaseFold = 9, kPhaseSelect = 10, kPhaseProbePack = 11,
              kPhaseProbeSeg = 12, kPhaseProbeOut = 13, kPhaseEncTile = 14, kPhaseEncScan = 15,
              kPhaseEncIndex = 16, kPhaseEncData = 17, kPhaseTableOpen = 18, kPhaseTableGet = 19,
-             kNumPhases = 20 };
+             kPhaseScanRank = 20, kPhaseScanEmit = 21, kNumPhases = 22 };
 void phase_begin(int phase, hipStream_t s);
 void phase_end(int phase, hipStream_t s);
 
@@ -146,6 +146,7 @@ struct TableDesc {
     const uint32_t* counts;   // [nblocks] entries per block (<= 256)
     const uint16_t* pos;      // [nblocks * 256] entry starts within each block
     const uint64_t* kpos;     // [nblocks + 1] start of index record b in index; [nblocks] = index_len
+    const uint64_t* ebase;    // [nblocks + 1] entries before block b; [nblocks] = the table's entries
     uint64_t nblocks;
 };
 enum : uint32_t { kTabErrBig = 1, kTabErrDense = 2, kTabErrOrder = 4, kTabErrIndexLen = 8, kTabErrIndexRec = 16 };
@@ -181,6 +182,39 @@ struct TableGetArgs {
 hipError_t table_fill(const TableOpenArgs& a, hipStream_t s);
 hipError_t table_check(const TableOpenArgs& a, hipStream_t s);
 hipError_t table_get(const TableGetArgs& a, hipStream_t s);
+// Range scans over open tables (vbf_table_scan.hip).  P = nranges * nsst (range, table) pairs in
+// range-major order; `total` candidate entries (the sum of cnt), one merged slot each.
+enum : uint32_t { kScanKeepTombstones = 1, kScanEndExclusive = 2 };
+enum : uint32_t { kScanErrBounds = 1, kScanErrRank = 2 };
+struct TableScanArgs {
+    const uint8_t* bounds;      // device; lo_r / hi_r as in MultiSst
+    const uint64_t* bounds_off; // device, 2 * nranges + 1 absolute positions
+    uint64_t nranges;
+    uint32_t nsst, flags;
+    const TableDesc* tab;       // device, nsst entries, in the caller's table order
+    uint64_t* first;            // [P] rank of the pair's first candidate in its table (bounds pass)
+    uint64_t* cnt;              // [P + 1] candidates of the pair (bounds pass); [P] = 0
+    const uint64_t* cbase;      // [P + 1] exclusive scan of cnt; [P] = total
+    uint64_t total;
+    uint32_t* m_table;          // [total] merged slot -> table, -> entry start in data.db (rank pass)
+    uint32_t* m_pos;
+    uint64_t* m_keep;           // [total + 1] 1 when the slot's entry is listed, its key length then
+    uint64_t* m_len;            //             (rank pass; [total] = 0)
+    const uint64_t* opos;       // [total + 1] exclusive scans of m_keep / m_len
+    const uint64_t* kofs;
+    uint32_t* err;              // [0] kScanErr bits
+    uint64_t* range_off;        // outputs, each may be NULL (emit / keys passes)
+    uint8_t* keys;
+    uint64_t* key_off;
+    uint32_t* table_idx;
+    uint32_t* val_off;
+    uint64_t* created;
+    uint8_t* tomb;
+};
+hipError_t table_scan_bounds(const TableScanArgs& a, hipStream_t s);
+hipError_t table_scan_rank(const TableScanArgs& a, hipStream_t s);
+hipError_t table_scan_emit(const TableScanArgs& a, hipStream_t s);
+hipError_t table_scan_keys(const TableScanArgs& a, hipStream_t s);
 // Batched probe across SSTs (vbf_multi.hip).
 struct MultiSst {
     const uint32_t* words;

@@ -5,9 +5,11 @@
 // src/fs/mod.rs:334-389) -- and keeps the strictly newest hit over the SSTs
 // (DataStore::search_key_in_sstables, src/db/store.rs:579-612).
 //
-// A table handle holds, next to the borrowed data.db / index.db / block starts, three side tables
+// A table handle holds, next to the borrowed data.db / index.db / block starts, four side tables
 // built once at open:
 //   counts[nblocks]        entries per block           (k_sst_walk, vbf_sst.hip)
+//   ebase[nblocks + 1] u64 entries before block b      (exclusive scan of counts; the range scans'
+//                                                       entry ranks, vbf_table_scan.hip)
 //   pos[nblocks][256] u16  entry starts in each block  (k_sst_walk; k_table_fill expands the blocks
 //                                                       of one key length, which the walk leaves out)
 //   kpos[nblocks + 1] u64  start of index record b     (exclusive scan of the blocks' last-key
@@ -19,53 +21,24 @@
 //   k_table_get : one lane per key.  The lane loops over its candidate tables in order with the
 //                 fold in registers (no atomics: ties go to the earlier table by construction); per
 //                 table a binary search over the index keys, then one over the chosen block's entry
-//                 starts.  Keys are compared as Rust's `Ord for [u8]` in byte-swapped 8-byte words
-//                 read at their own byte offsets (never past a key's end), the tail bytewise.
+//                 starts (vbf_table_search.hpp, shared with the range scans).  Keys are compared
+//                 as Rust's `Ord for [u8]` in byte-swapped 8-byte words read at their own byte
+//                 offsets (never past a key's end), the tail bytewise.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "vbf_kernels.hpp"
+#include "vbf_table_search.hpp"
 
 namespace vbf {
 
 namespace {
 
 constexpr uint32_t kTabWaves = 4;      // waves per workgroup of the open passes; one block per wave
-constexpr uint32_t kTabMaxEnt = 256;   // pos slots per block (vbf_sst.hip's kMaxEnt)
 constexpr uint32_t kTabMaxBlock = 4096;
 constexpr uint32_t kTabFixed = 17;     // key_len + value offset + created_at + tombstone
-
-__device__ __forceinline__ uint64_t ld8(const uint8_t* p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-__device__ __forceinline__ uint32_t ld4(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-
-// Rust `Ord for [u8]` (cmp_bytes of keyhash.hpp is the bytewise statement): -1 / 0 / 1.  Whole
-// 8-byte words are read at the keys' own byte offsets, only while both keys have 8 bytes left; the
-// last 0..7 bytes go bytewise.  No byte outside [a, a + la) or [b, b + lb) is read.
-__device__ __forceinline__ int cmp_keys(const uint8_t* a, uint64_t la, const uint8_t* b, uint64_t lb) {
-    const uint64_t n = la < lb ? la : lb;
-    uint64_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-        const uint64_t x = ld8(a + i), y = ld8(b + i);
-        if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;
-    }
-    uint64_t x = 0, y = 0;
-    for (; i < n; ++i) {
-        x = (x << 8) | a[i];
-        y = (y << 8) | b[i];
-    }
-    if (x != y) return x < y ? -1 : 1;
-    return la < lb ? -1 : (la > lb ? 1 : 0);
-}
 
 __device__ __forceinline__ void tab_error(uint32_t* err, uint32_t bits, uint64_t block, uint64_t entry) {
     atomicOr(err, bits);
@@ -153,35 +126,13 @@ __global__ __launch_bounds__(256) void k_table_get(TableGetArgs a) {
     for (uint32_t t = 0; t < a.nsst; ++t) {
         if (a.cand && !a.cand[j * a.nsst + t]) continue;
         const TableDesc& d = a.tab[t];
-        const uint64_t nb = d.nblocks;
         // index step: the first record with key >= q; none -> the table is skipped
-        uint64_t lo = 0, hi = nb;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            const uint64_t r0 = d.kpos[mid], r1 = d.kpos[mid + 1];
-            if (cmp_keys(d.index + r0 + 4, r1 - r0 - 8, q, ql) < 0) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo == nb) continue;
+        const uint64_t lo = index_lower(d, q, ql);
+        if (lo == d.nblocks) continue;
         // block step: equality inside that block
-        const uint8_t* blk = d.data + d.blocks[lo];
-        const uint16_t* ps = d.pos + lo * kTabMaxEnt;
-        uint32_t el = 0, eh = d.counts[lo];
-        const uint8_t* hit = nullptr;
-        uint32_t hl = 0;
-        while (el < eh) {
-            const uint32_t mid = (el + eh) >> 1;
-            const uint8_t* ent = blk + ps[mid];
-            const uint32_t L = ld4(ent);
-            const int c = cmp_keys(ent + 4, L, q, ql);
-            if (c == 0) {
-                hit = ent;
-                hl = L;
-                break;
-            }
-            if (c < 0) el = mid + 1;
-            else eh = mid;
-        }
+        const BlockPos at = block_lower(d, lo, q, ql);
+        const uint8_t* hit = at.hit;
+        const uint32_t hl = at.hit_len;
         if (!hit) continue;
         const uint64_t created = ld8(hit + 8 + hl);
         if (created > best) {

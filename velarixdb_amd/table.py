@@ -13,13 +13,18 @@ in every table in one launch (vbf_table_get_host, velarixdb_amd/csrc/vbf_table.h
   get_many(keys, tables, filters=None) -> GetResult(found, table, val_offsets, created_ms)
       found 0 = nowhere, 1 = live, 2 = tombstone; table = index into `tables` (0xFFFFFFFF when
       found == 0).  filters (one BloomFilter per table) only prune work: the answers are the same.
+  scan_many(ranges, tables, keep_tombstones=False, end_exclusive=False)
+      -> ScanResult(range_off, keys, key_off, table, val_offsets, created_ms, tombstones)
+      the key side of DataStore::seek (src/range/range_iterator.rs:47-60) for a batch of (lo, hi)
+      ranges: per range, in key order, every key inside the bounds that get_many would find, with
+      get_many's answer for it (C ABI vbf_table_scan_host, velarixdb_amd/csrc/vbf_table_scan.hip).
 """
 import ctypes
 from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import VbfError, call, lib
+from ._lib import VBF_SCAN_END_EXCLUSIVE, VBF_SCAN_KEEP_TOMBSTONES, VbfError, call, lib
 from .filter import _raise
 from .keys import HostBatch, pack
 from .sst import _buf, read_sst_files
@@ -115,4 +120,51 @@ def get_many(keys, tables, filters=None):
              vp(res.val_offsets), vp(res.created_ms))
     except VbfError as e:
         _raise("table_get", e)
+    return res
+
+
+@dataclass
+class ScanResult:
+    range_off: np.ndarray    # uint64 [nranges + 1]: range r lists outputs range_off[r] .. range_off[r+1]
+    keys: np.ndarray         # uint8: the listed keys back to back
+    key_off: np.ndarray      # uint64 [n + 1]: key i = keys[key_off[i] .. key_off[i+1])
+    table: np.ndarray        # uint32 index into `tables` of the winning entry
+    val_offsets: np.ndarray  # uint32
+    created_ms: np.ndarray   # uint64
+    tombstones: np.ndarray   # uint8: 1 only with keep_tombstones
+
+    def range(self, r):
+        """(key bytes, table, val_offset, created_ms, tombstone) for every entry of range r, in key order."""
+        kb = self.keys.tobytes()
+        for i in range(int(self.range_off[r]), int(self.range_off[r + 1])):
+            yield (kb[int(self.key_off[i]):int(self.key_off[i + 1])], int(self.table[i]), int(self.val_offsets[i]),
+                   int(self.created_ms[i]), int(self.tombstones[i]))
+
+
+def scan_many(ranges, tables, keep_tombstones=False, end_exclusive=False):
+    """For every (lo, hi) of `ranges` (bytes, both ends inclusive unless end_exclusive) the keys of
+    `tables` inside it that get_many over the same tables finds, ascending, with its answers.  One
+    size query, then one filling call."""
+    ranges = [(bytes(lo), bytes(hi)) for lo, hi in ranges]
+    tables = list(tables)
+    nr, nsst = len(ranges), len(tables)
+    flat = [b for pair in ranges for b in pair]
+    bounds = np.frombuffer(b"".join(flat) + b"\0", np.uint8)  # never NULL
+    boff = np.concatenate([[0], np.cumsum([len(b) for b in flat], dtype=np.uint64)]).astype(np.uint64)
+    th = (ctypes.c_void_p * max(nsst, 1))(*[t._h.value for t in tables])
+    flags = (VBF_SCAN_KEEP_TOMBSTONES if keep_tombstones else 0) | (VBF_SCAN_END_EXCLUSIVE if end_exclusive else 0)
+    n, kb = ctypes.c_uint64(), ctypes.c_uint64()
+    head = (bounds.ctypes.data, boff.ctypes.data, nr, nsst, th, flags)
+    try:
+        call("vbf_table_scan_host", *head, None, None, 0, None, None, None, None, None, 0, ctypes.byref(n),
+             ctypes.byref(kb))
+        res = ScanResult(np.zeros(nr + 1, np.uint64), np.zeros(kb.value, np.uint8), np.zeros(n.value + 1, np.uint64),
+                         np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint64),
+                         np.zeros(n.value, np.uint8))
+        vp = lambda x: x.ctypes.data if x.size else None
+        call("vbf_table_scan_host", *head, res.range_off.ctypes.data, vp(res.keys), kb.value, res.key_off.ctypes.data,
+             vp(res.table), vp(res.val_offsets), vp(res.created_ms), vp(res.tombstones), n.value, ctypes.byref(n),
+             ctypes.byref(kb))
+    except VbfError as e:
+        _raise("table_scan", e)
     return res
