@@ -48,6 +48,23 @@
  *
  * Filter words.  ceil(m/32) uint32 words, bit i = words[i/32] bit (i%32): the storage of
  * bit-vec 0.6.3 `BitVec<u32>` (Cargo.toml:19).  Builds OR into existing bits, never clear.
+ *
+ * Threads.  Every `_host` entry point and every call on a handle (vbf_filter_*, vbf_table_*) may
+ * be made from any number of threads at once, on the same or on different devices, with the
+ * answers a single caller gets.  Calls on one filter are ordered by the filter's lock, as the
+ * reference's Mutex<BitVec> orders them; a vbf_table is immutable once opened, so any number of
+ * gets and scans may read it together.  Per device the library serialises what shares its
+ * staging: vbf_build_host, vbf_probe_host and the filters' set_host / contains_host / words
+ * copies take turns on the device's two staging streams, and the other `_host` entry points
+ * (sst_decode, sst_encode, rebuild_from_sst, multi_probe, compact_merge, compact_write,
+ * table_open, table_get, table_scan) take turns on its shared stream, each from its first upload
+ * to its last download; the two groups overlap each other, and devices never wait for each
+ * other.  A call that spans several devices (vbf_multi_probe_host over filters on several GPUs)
+ * holds one device at a time.  Locks are taken filters first (in address order), then the device.
+ * The `_dev` entry points take no device lock: their workspace is cached per stream and belongs
+ * to the caller's stream, so two threads must not drive one stream through the library at the
+ * same time (different streams are independent).  vbf_release_workspaces waits for the `_host`
+ * calls in flight and keeps new ones out while it frees; no `_dev` call may be in flight then.
  */
 #ifndef VBF_H
 #define VBF_H
@@ -129,7 +146,10 @@ int vbf_build_dev_ex(const uint8_t* keys, const uint64_t* offsets, uint64_t stri
  * vbf_release_workspaces.  When that allocation fails the build retries with half the chunk, down
  * to 2^28 indices (VBF_WS_MAX_BYTES caps the workspace the same way). */
 uint64_t vbf_build_workspace_bytes(uint64_t n, uint32_t m, uint32_t k);
-/* Free every cached workspace (synchronizes the streams that own them). */
+/* Free every cached workspace (synchronizes the streams that own them).  Safe beside `_host` and
+ * handle calls on other threads: it waits for those in flight on every device and holds new ones
+ * back until the buffers are gone (they allocate again).  The `_dev` workspaces belong to the
+ * callers' streams: no `_dev` call may be running, or be started, while this runs. */
 int vbf_release_workspaces(void);
 /* Adds the number of keys the filter answers "present" for to *count_dev (device u64). */
 int vbf_probe_count_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
@@ -640,7 +660,8 @@ int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t st
  * Work is O(candidates x nsst x log(entries per table)) key comparisons: every candidate searches
  * its key in every other table.  That suits short and medium ranges; it is not a merge-path scan.
  * Workspace (cached per stream like every other): 40 bytes per candidate + 24 per (range, table)
- * pair, plus the scans' scratch.
+ * pair, plus the scans' scratch.  It belongs to the caller's stream, so two threads must not drive
+ * one stream through the library at the same time ("Threads" above); _host callers need no care.
  * _dev synchronises `stream` three times (the table descriptors' upload, the candidate total, the
  * two sizes); the output passes stay queued on it.  _host is synchronous. */
 #define VBF_SCAN_KEEP_TOMBSTONES 1u

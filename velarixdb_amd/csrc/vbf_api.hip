@@ -419,6 +419,14 @@ void par_memcpy(void* dst, const void* src, size_t n) {
 
 struct Staging {
     std::mutex mu;
+    // The device's shared stream (filter_stream) and the workspaces cached on it belong to one host
+    // entry point at a time: held from before the call's first get_workspace on that stream until
+    // after its last hipStreamSynchronize (HostCall).  A lock of its own, not `mu`: `mu` guards the
+    // two staging streams and their buffers, which no holder of host_mu touches, so a long
+    // vbf_build_host keeps overlapping the read path's gets and scans as before.
+    // Lock order: filter lock(s) (Storage::mu, address order), then host_mu.  No holder waits for a
+    // device worker's job (jobs_cv) or takes another device's host_mu.
+    std::mutex host_mu;
     int device = -1;
     hipStream_t stream[2] = {nullptr, nullptr};
     hipEvent_t done[2] = {nullptr, nullptr};
@@ -542,6 +550,12 @@ Staging* staging_for(int device) {
     if (!g_staging[device]) g_staging[device].reset(new Staging());
     return g_staging[device].get();
 }
+
+// One host entry point's turn on `device`'s shared stream and its workspaces (Staging::host_mu).
+struct HostCall {
+    std::unique_lock<std::mutex> lk;
+    explicit HostCall(int device) : lk(staging_for(device)->host_mu) {}
+};
 
 // Streams host keys through the staging buffers, calling launch(batch_on_device, first_key,
 // buffer_index, stream) per chunk.  After the loop both streams are synchronized.
@@ -1404,11 +1418,22 @@ uint64_t vbf_build_workspace_bytes(uint64_t n, uint32_t m, uint32_t k) {
 }
 
 int vbf_release_workspaces(void) {
-    std::lock_guard<std::mutex> lk(g_ws_mu);
     if (hip_forked()) {  // the parent's buffers: forget them, free nothing
+        std::lock_guard<std::mutex> lk(g_ws_mu);
         g_ws.clear();
         return ok();
     }
+    // every device's host calls are kept out while their workspaces are freed: a new caller waits
+    // in staging_for, one in flight is waited for.  _dev calls on caller streams are the caller's
+    // to keep away (vbf.h).
+    std::lock_guard<std::mutex> sl(g_staging_mu);
+    std::vector<std::unique_lock<std::mutex>> held;
+    for (auto& st : g_staging)
+        if (st) {
+            held.emplace_back(st->host_mu);
+            held.emplace_back(st->mu);
+        }
+    std::lock_guard<std::mutex> lk(g_ws_mu);
     for (auto& w : g_ws) {
         int prev = -1;
         (void)hipGetDevice(&prev);
@@ -2327,6 +2352,7 @@ int vbf_sst_decode_host(const uint8_t* data, uint64_t len, const uint8_t* index,
     DEVICE_SCOPE(device);
     hipStream_t s;
     if ((rc = filter_stream(device, &s))) return rc;
+    HostCall turn(device);
     // device image: data | blocks | then the outputs (count pass first, to size them)
     const uint64_t o_blk = align256(len), o_end = o_blk + align256(blk.size() * 4);
     void* in = nullptr;
@@ -2397,6 +2423,7 @@ int vbf_sst_encode_host(const uint8_t* keys, const uint64_t* offsets, uint64_t s
     hipStream_t s;
     int rc = filter_stream(device, &s);
     if (rc) return rc;
+    HostCall turn(device);
     // device image: keys | offsets | val | created | tombstones | data | index | blocks, the outputs
     // at the sizes that always suffice (or the caller's capacity when that is smaller)
     const uint64_t dcap = data ? std::min(data_cap, kb + 17 * n) : 0, icap = index ? std::min(index_cap, kb + 8 * n) : 0;
@@ -2494,6 +2521,7 @@ int vbf_filter_rebuild_from_sst_host(vbf_filter* f, const uint8_t* data, uint64_
     DEVICE_SCOPE(s.device);
     hipStream_t st;
     if ((rc = filter_stream(s.device, &st))) return rc;
+    HostCall turn(s.device);  // after the filter's lock and its drain
     const uint64_t o_blk = align256(len), o_end = o_blk + align256(blk.size() * 4);
     void* in = nullptr;
     if ((rc = get_workspace(st, o_end, &in, kWsSstInput))) return rc;
@@ -2754,6 +2782,7 @@ int multi_probe_host_device(const uint8_t* keys, const uint64_t* offsets, uint64
     hipStream_t s;
     int rc = filter_stream(device, &s);
     if (rc) return rc;
+    HostCall turn(device);  // this device's part only: the multi-device path takes each in turn
     const uint64_t kbytes = offsets ? offsets[n] - offsets[0] : n * stride;
     const uint64_t o_off = align256(kbytes), o_out = o_off + align256(offsets ? (n + 1) * 8 : 0);
     void* ws = nullptr;
@@ -3101,6 +3130,7 @@ int vbf_compact_merge_host(const uint8_t* keys, const uint64_t* offsets, const i
     DEVICE_SCOPE(device);
     hipStream_t s;
     if ((rc = filter_stream(device, &s))) return rc;
+    HostCall turn(device);
     const uint64_t kb = total ? offsets[total] : 0, mkb = map_n ? map_off[map_n] : 0;
     const uint64_t o_off = align256(kb), o_cr = o_off + align256((total + 1) * 8), o_tb = o_cr + align256(total * 8);
     const uint64_t o_mk = o_tb + align256(total), o_mo = o_mk + align256(mkb), o_mt = o_mo + align256((map_n + 1) * 8);
@@ -3166,6 +3196,9 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
     DEVICE_SCOPE(device);
     hipStream_t s;
     if ((rc = filter_stream(device, &s))) return rc;
+    // The one place a filter lock is taken under the device's: the merged table's filter is created
+    // below and no other thread can reach it before this call returns it.
+    HostCall turn(device);
     const bool want_upd = upd_ids && upd_time;
     const uint64_t kb = offsets[total], mkb = map_n ? map_off[map_n] : 0;
     const uint64_t o_off = align256(kb), o_cr = o_off + align256((total + 1) * 8), o_tb = o_cr + align256(total * 8);
@@ -3435,6 +3468,7 @@ int vbf_table_open_host(const uint8_t* data, uint64_t data_len, const uint8_t* i
         t->device = device;
         hipStream_t s;
         if ((rc = filter_stream(device, &s))) return rc;
+        HostCall turn(device);
         const uint64_t o_idx = align256(data_len), o_blk = o_idx + align256(index_len);
         const uint64_t bytes = o_blk + align256(blk.size() * 4);
         uint8_t* d = nullptr;
@@ -3516,16 +3550,25 @@ int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t st
     }
     const int device = tables[0]->device;
     if (filters)
-        for (uint32_t i = 0; i < nsst; ++i) {
+        for (uint32_t i = 0; i < nsst; ++i)
             if (!filters[i]) return fail(VBF_EINVAL, "filters[%u] is NULL", i);
-            if (filters[i]->bits->device != device)
-                return fail(VBF_EINVAL, "filters[%u] lives on device %d, the tables on %d", i,
-                            filters[i]->bits->device, device);
-        }
     try {
+        // Lock order: the filters' locks and their drain (which waits for a device's worker) come
+        // first, then the device's host-call lock -- as vbf_multi_probe_host and
+        // vbf_filter_rebuild_from_sst_host take them.  Staging the keys before the filter locks, as
+        // this call once did, would hold the device while waiting for a filter whose holder waits
+        // for the device.
+        MultiLock lk(filters, filters ? nsst : 0);
+        if ((rc = lk.drain())) return rc;
+        if (filters)
+            for (uint32_t i = 0; i < nsst; ++i)
+                if (filters[i]->bits->device != device)
+                    return fail(VBF_EINVAL, "filters[%u] lives on device %d, the tables on %d", i,
+                                filters[i]->bits->device, device);
         DEVICE_SCOPE(device);
         hipStream_t s;
         if ((rc = filter_stream(device, &s))) return rc;
+        HostCall turn(device);
         const uint64_t kbytes = offsets ? offsets[n] - offsets[0] : n * stride;
         const uint64_t o_off = align256(kbytes), o_cand = o_off + align256(offsets ? (n + 1) * 8 : 0);
         const uint64_t o_found = o_cand + align256(filters ? n * nsst : 0), o_idx = o_found + align256(n);
@@ -3557,8 +3600,6 @@ int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t st
                 boff.push_back(bounds.size());
             }
             bounds.push_back(0);  // never NULL
-            MultiLock lk(filters, nsst);
-            if ((rc = lk.drain())) return rc;
             if ((rc = multi_probe(d_keys, d_off, stride, n, 1, nsst, filters, bounds.data(), boff.data(), d_cand, s)))
                 return rc;
         }
@@ -3775,6 +3816,7 @@ int vbf_table_scan_host(const uint8_t* bounds, const uint64_t* bounds_off, uint6
         DEVICE_SCOPE(device);
         hipStream_t s;
         if ((rc = filter_stream(device, &s))) return rc;
+        HostCall turn(device);
         // bounds and their offsets, rebased to positions in the device copy
         const uint64_t b0 = bounds_off[0], bbytes = bounds_off[2 * nranges] - b0;
         const uint64_t o_boff = align256(bbytes);
