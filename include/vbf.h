@@ -37,6 +37,11 @@
  *   DataFileNode::find_entry           src/fs/mod.rs:334-389       -> vbf_table_get_* (block step)
  *   DataStore::search_key_in_sstables  src/db/store.rs:579-612     -> vbf_table_open_* + vbf_table_get_*
  *   DataStore::seek (a stub there)     src/range/range_iterator.rs:47-60 -> vbf_table_scan_* (the key side)
+ *   ValueLog::get                      src/vlog/v_log.rs:205-207   -> vbf_vlog_open_* + vbf_vlog_get_*
+ *   VLogFileNode::get                  src/fs/mod.rs:470-518       -> vbf_vlog_get_* (header, key skip, value)
+ *   DataStore::get_value_from_vlog     src/db/store.rs:628-641     -> vbf_vlog_get_* (tombstone -> no value)
+ *   ValueLog::append                   src/vlog/v_log.rs:173-196   -> vbf_vlog_encode_* (val_offsets)
+ *   ValueLogEntry::serialize           src/vlog/v_log.rs:291-309   -> vbf_vlog_encode_* (the bytes)
  *
  * Key batches.  `keys` holds the key bytes back to back.  When `offsets` is non-NULL it has
  * n+1 nondecreasing entries and key j is keys[offsets[j] .. offsets[j+1]) (positions are
@@ -49,17 +54,17 @@
  * Filter words.  ceil(m/32) uint32 words, bit i = words[i/32] bit (i%32): the storage of
  * bit-vec 0.6.3 `BitVec<u32>` (Cargo.toml:19).  Builds OR into existing bits, never clear.
  *
- * Threads.  Every `_host` entry point and every call on a handle (vbf_filter_*, vbf_table_*) may
- * be made from any number of threads at once, on the same or on different devices, with the
- * answers a single caller gets.  Calls on one filter are ordered by the filter's lock, as the
- * reference's Mutex<BitVec> orders them; a vbf_table is immutable once opened, so any number of
- * gets and scans may read it together.  Per device the library serialises what shares its
- * staging: vbf_build_host, vbf_probe_host and the filters' set_host / contains_host / words
- * copies take turns on the device's two staging streams, and the other `_host` entry points
+ * Threads.  Every `_host` entry point and every call on a handle (vbf_filter_*, vbf_table_*,
+ * vbf_vlog_*) may be made from any number of threads at once, on the same or on different devices,
+ * with the answers a single caller gets.  Calls on one filter are ordered by the filter's lock, as
+ * the reference's Mutex<BitVec> orders them; a vbf_table and a vbf_vlog are immutable once opened,
+ * so any number of gets and scans may read them together.  Per device the library serialises what
+ * shares its staging: vbf_build_host, vbf_probe_host and the filters' set_host / contains_host /
+ * words copies take turns on the device's two staging streams, and the other `_host` entry points
  * (sst_decode, sst_encode, rebuild_from_sst, multi_probe, compact_merge, compact_write,
- * table_open, table_get, table_scan) take turns on its shared stream, each from its first upload
- * to its last download; the two groups overlap each other, and devices never wait for each
- * other.  A call that spans several devices (vbf_multi_probe_host over filters on several GPUs)
+ * table_open, table_get, table_scan, vlog_open, vlog_get, vlog_encode) take turns on its shared
+ * stream, each from its first upload to its last download; the two groups overlap each other, and
+ * devices never wait for each other.  A call that spans several devices (vbf_multi_probe_host over filters on several GPUs)
  * holds one device at a time.  Locks are taken filters first (in address order), then the device.
  * The `_dev` entry points take no device lock: their workspace is cached per stream and belongs
  * to the caller's stream, so two threads must not drive one stream through the library at the
@@ -99,8 +104,11 @@ int vbf_device_count(int* count);
  * 11 partitioned-probe pack, 12 probe segment test, 13 probe answers, 14 SST-encode tile tables,
  * 15 encode table scan + block count, 16 index.db emit, 17 data.db emit, 18 table open (side
  * tables + validation), 19 table get, 20 table scan bounds + rank (with their scans), 21 table scan
- * emit + key copy.
- * vbf_profile_read synchronizes, returns per-phase summed ms and launch counts, and resets. */
+ * emit + key copy, 22 value-log fetch sizes + scan, 23 value-log fetch copy, 24 value-log encode
+ * (its check and its copy).
+ * vbf_profile_read synchronizes, returns per-phase summed ms and launch counts, and resets; it
+ * fills the first `nphases` phases, so a caller built against a shorter list keeps working (the
+ * later phases' records are dropped). */
 int vbf_profile_enable(int on);
 int vbf_profile_read(double* ms, uint64_t* launches, int nphases);
 
@@ -550,7 +558,7 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
  * an equal key (Table::get, src/sst/table.rs:184-193; DataFileNode::find_entry, src/fs/mod.rs:334-389)
  * and keeps the strictly newest hit over the SSTs (DataStore::search_key_in_sstables,
  * src/db/store.rs:579-612).  Here a table is opened once on the device and a batch of keys is
- * looked up in every table in one launch; only the value-log read is left to the host.
+ * looked up in every table in one launch; the value-log read that follows is vbf_vlog_get_* below.
  *
  * A vbf_table holds data.db, index.db and the block starts on the device plus side tables built at
  * open (every block's entry starts and count, the entries before every block, the start of every
@@ -676,6 +684,101 @@ int vbf_table_scan_host(const uint8_t* bounds, const uint64_t* bounds_off, uint6
                         uint64_t keys_cap, uint64_t* key_off, uint32_t* table_idx, uint32_t* val_offsets,
                         uint64_t* created_ms, uint8_t* tombstones, uint64_t entries_cap, uint64_t* n_out,
                         uint64_t* key_bytes);
+
+/* ---- batched value-log reads and appends ----
+ * The last step of a get and the first of a put.  The value log (src/vlog/v_log.rs) is one file of
+ * entries laid back to back, little-endian, no padding and no index (ValueLogEntry::serialize,
+ * v_log.rs:291-309):
+ *     u32 key_len | u32 val_len | u64 created_at ms | u8 tombstone | key | value
+ * The header is 17 bytes; an entry's offset is the file position of its first byte, and data.db
+ * stores it as u32 (block_manager.rs:91,183).  ValueLog::get (v_log.rs:205-207) -> VLogFileNode::get
+ * (fs/mod.rs:470-518): an offset at or past the end of the file is Ok(None); otherwise one header is
+ * read, the key skipped and the value returned, with no check of the key or of created_at;
+ * DataStore::get_value_from_vlog (db/store.rs:628-641) turns a tombstone (byte == 1, any other byte
+ * is live) into None.  ValueLog::append (v_log.rs:173-196) writes the entry at the file's size and
+ * returns that position.
+ * Two readings of this library's: a zero-length value is an ordinary value, and so is a zero-length
+ * key (the reference's load_buffer! treats a 0-byte read as UnexpectedEof, so its get of either
+ * fails); an entry whose header or body runs past the end of the log is reported as bad, per item
+ * (the reference's single read would return a short buffer there; no short value is returned here).
+ * Out of scope: ValueLog::recover and the GC's chunk read (a serial walk of an unindexed file), hole
+ * punching, file I/O.
+ *
+ * A vbf_vlog is a window of the log on a device: bytes[0..len) are the file's bytes
+ * [base, base + len).  `base` is the log's tail: the GC punches the front of the file away, so a
+ * caller uploads only what is live.  Open parses nothing (there is no index to validate against);
+ * len == 0 opens and holds nothing; base + len must not wrap.  The handle is immutable, like
+ * vbf_table. */
+typedef struct vbf_vlog vbf_vlog;
+/* Borrows the caller's device buffer on the current device; it must outlive the handle. */
+int vbf_vlog_open_dev(const uint8_t* bytes, uint64_t len, uint64_t base, vbf_vlog** out);
+/* Uploads host bytes to `device` into a buffer the handle owns. */
+int vbf_vlog_open_host(const uint8_t* bytes, uint64_t len, uint64_t base, int device, vbf_vlog** out);
+void vbf_vlog_free(vbf_vlog* v);
+uint64_t vbf_vlog_bytes(const vbf_vlog* v);
+uint64_t vbf_vlog_base(const vbf_vlog* v);
+int vbf_vlog_device(const vbf_vlog* v);
+
+/* The batched fetch.  Item j reads the entry at file position val_offsets[j]; `found`
+ * (vbf_table_get_*'s output, passed straight through) restricts the fetch to the items with
+ * found[j] == 1, NULL fetches every item.  keys / offsets / stride: the layout of every entry point;
+ * keys == NULL means no check, otherwise the entry's key must equal key j in length and in bytes.
+ * status[j]: */
+#define VBF_VLOG_SKIPPED 0       /* the `found` mask excluded item j                               */
+#define VBF_VLOG_VALUE 1         /* the value was fetched                                          */
+#define VBF_VLOG_TOMBSTONE 2     /* the entry's byte is 1: no value is returned                    */
+#define VBF_VLOG_NONE 3          /* offset >= base + len: the reference's Ok(None)                 */
+#define VBF_VLOG_BAD 4           /* offset < base, or the header or the body crosses base + len    */
+                                 /* (computed in 64 bits: key_len = val_len = 0xFFFFFFFF is BAD)   */
+#define VBF_VLOG_KEY_MISMATCH 5  /* a key was given and it differs from the entry's key            */
+/* The checks run in that order of precedence: SKIPPED, NONE, BAD, KEY_MISMATCH (also for a
+ * tombstone of another key), TOMBSTONE, VALUE.
+ * Only status 1 has a value: item j's is values[value_off[j] .. value_off[j+1]); value_off has
+ * n + 1 entries, starts at 0 and gives zero length to every other status.  Values are in item
+ * order; duplicated offsets give duplicated values.  A bad item never fails the call.
+ * *value_bytes (= value_off[n]) is always written.  values == NULL is the size query: status and
+ * value_off, where given, are still filled.  values given with values_cap < *value_bytes is
+ * VBF_EINVAL with the size written and no output array touched (the encoder's convention).
+ * n == 0 is VBF_OK with no device work (_host then writes value_off[0] = 0).  At most 2^31 - 2 items.
+ * Every argument check (NULL handle, NULL val_offsets with n > 0, NULL value_bytes, the item limit;
+ * in _host also a descending `offsets`) runs on the host before any HIP call.  _dev runs on the
+ * current device, which must be the handle's (VBF_EINVAL otherwise, checked first of the device
+ * work).  _dev synchronises `stream` once, to read the byte total; the copy stays queued.
+ * Workspace (cached per stream like every other, so the "Threads" rule for `_dev` holds): 25 bytes
+ * per item plus the scan's scratch.  _host: every array in host memory, synchronous, on the
+ * handle's device. */
+int vbf_vlog_get_dev(const vbf_vlog* v, const uint32_t* val_offsets, const uint8_t* found, uint64_t n,
+                     const uint8_t* keys, const uint64_t* offsets, uint64_t stride,
+                     uint8_t* status, uint8_t* values, uint64_t values_cap, uint64_t* value_off,
+                     uint64_t* value_bytes, void* stream);
+int vbf_vlog_get_host(const vbf_vlog* v, const uint32_t* val_offsets, const uint8_t* found, uint64_t n,
+                      const uint8_t* keys, const uint64_t* offsets, uint64_t stride,
+                      uint8_t* status, uint8_t* values, uint64_t values_cap, uint64_t* value_off,
+                      uint64_t* value_bytes);
+
+/* The batched append.  Entry j = (key j, values[value_off[j] .. value_off[j+1]), created_ms[j],
+ * tombstones[j]) is serialised at base + the sum of the earlier entries' sizes, as ValueLog::append
+ * places it when the file's size is `base`; val_offsets[j] is that position, exactly what
+ * vbf_sst_encode_* takes.  Keys in the layout of every entry point; value_off has n + 1
+ * nondecreasing absolute positions in `values` and need not start at 0, like `offsets`.
+ * created_ms / tombstones may be NULL (zeros); a tombstone byte != 0 is written as 1.
+ * *out_len (the bytes appended) is always written.  out == NULL && val_offsets == NULL is the size
+ * query; either may be NULL on its own.  out given with out_cap < *out_len is VBF_EINVAL with
+ * *out_len written and nothing else.  n == 0 is VBF_OK with *out_len = 0 and no device work.
+ * VBF_EINVAL: an entry that would start at 2^32 or beyond (data.db could not address it; where
+ * base + 17 (n - 1) already reaches 2^32 this is decided before any device work), descending
+ * offsets or value_off, a key or value longer than 2^32 - 1 bytes.  _dev (device arrays) checks the
+ * two offset arrays in a first pass and synchronises the stream once (their ends and that pass's
+ * verdict); the copy stays queued.  _host (host arrays, encoded on `device`, synchronous) checks
+ * everything on the host before any HIP call, and its size query needs no device. */
+int vbf_vlog_encode_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                        const uint8_t* values, const uint64_t* value_off,
+                        const int64_t* created_ms, const uint8_t* tombstones, uint64_t base,
+                        uint8_t* out, uint64_t out_cap, uint64_t* out_len, uint32_t* val_offsets, void* stream);
+int vbf_vlog_encode_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                         const uint8_t* values, const uint64_t* value_off,
+                         const int64_t* created_ms, const uint8_t* tombstones, uint64_t base,
+                         uint8_t* out, uint64_t out_cap, uint64_t* out_len, uint32_t* val_offsets, int device);
 
 #ifdef __cplusplus
 }

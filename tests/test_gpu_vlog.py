@@ -1,0 +1,549 @@
+"""GPU parity for the batched value-log reads and appends (vbf_vlog_*).
+
+Checker: tests/vlog_ref.py (pinned to the reference's fixture by tests/test_vlog_ref.py).  Every
+comparison is exact equality on status, value_off, value_bytes and the value bytes, through _dev
+(torch buffers with 0xA5 guard bytes around every output, the log borrowed at byte shifts 0, 1 and
+7) and through _host."""
+import ctypes
+import functools
+import os
+
+import numpy as np
+import pytest
+
+import scan_cases as sc
+import sst_get_ref as ref
+import vlog_ref as vr
+from conftest import GOLDEN
+
+pytestmark = pytest.mark.gpu
+GUARD, PAD = 0xA5, 16
+SHIFTS = (0, 1, 7)
+T0 = sc.T0
+SLICE = 16384  # kVlogSlice of csrc/vbf_kernels.hpp: the copy's workgroups own this many output bytes
+
+
+# ---- buffers --------------------------------------------------------------------------------
+
+def _np(b):
+    return np.frombuffer(bytes(b), np.uint8)
+
+
+def _up(a, shift=0):
+    """-> (tensor kept alive, pointer) of a's bytes on the device, `shift` bytes into an allocation."""
+    import torch
+    raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    t = torch.full((raw.size + shift + 16,), 0xEE, dtype=torch.uint8, device="cuda:0")
+    if raw.size:
+        t[shift:shift + raw.size] = torch.from_numpy(raw.copy()).to("cuda:0")
+    return t, ctypes.c_void_p(t.data_ptr() + shift)
+
+
+def _out(nbytes, shift=0):
+    import torch
+    t = torch.full((PAD + shift + nbytes + PAD,), GUARD, dtype=torch.uint8, device="cuda:0")
+    return t, ctypes.c_void_p(t.data_ptr() + PAD + shift)
+
+
+def _down(t, nbytes, dtype, shift=0):
+    h = t.cpu().numpy()
+    assert (h[:PAD + shift] == GUARD).all() and (h[PAD + shift + nbytes:] == GUARD).all(), "wrote outside the output"
+    return h[PAD + shift:PAD + shift + nbytes].copy().view(dtype)
+
+
+def _stream():
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def pack_keys(keys, lead=0, stride=None):
+    """-> (bytes with `lead` filler bytes in front and one behind, u64 offsets from `lead` or None)"""
+    body = b"".join(keys)
+    if stride is not None:
+        assert all(len(k) == stride for k in keys) and lead == 0
+        return _np(body + b"\xEE"), None
+    offs = np.concatenate([[0], np.cumsum([len(k) for k in keys])]).astype(np.uint64) + np.uint64(lead)
+    return _np(b"\xEE" * lead + body + b"\xEE"), offs
+
+
+class Logs:
+    """One log opened through vbf_vlog_open_host and, borrowed at every byte shift, through
+    vbf_vlog_open_dev; freed on exit."""
+
+    def __init__(self, log, base=0):
+        self.log, self.base = bytes(log), base
+        self.host, self.dev, self.keep = None, [], []
+
+    def __enter__(self):
+        from velarixdb_amd._lib import lib
+        a = _np(self.log)
+        h = ctypes.c_void_p()
+        rc = lib.vbf_vlog_open_host(a.ctypes.data if a.size else None, a.size, self.base, 0, ctypes.byref(h))
+        assert rc == 0 and h.value, lib.vbf_last_error()
+        self.host = h
+        for shift in SHIFTS:
+            t, p = _up(a, shift)
+            d = ctypes.c_void_p()
+            rc = lib.vbf_vlog_open_dev(p if a.size else None, a.size, self.base, ctypes.byref(d))
+            assert rc == 0 and d.value, lib.vbf_last_error()
+            self.keep.append(t)
+            self.dev.append(d)
+        for h in [self.host] + self.dev:
+            assert (lib.vbf_vlog_bytes(h), lib.vbf_vlog_base(h), lib.vbf_vlog_device(h)) == (a.size, self.base, 0)
+        return self
+
+    def __exit__(self, *exc):
+        from velarixdb_amd._lib import lib
+        import torch
+        torch.cuda.synchronize()
+        for h in [self.host] + self.dev:
+            lib.vbf_vlog_free(h)
+
+
+# ---- calls ----------------------------------------------------------------------------------
+
+def get_dev(h, vo, found=None, keys=None, lead=0, stride=None, cut=None, dshift=0):
+    """vbf_vlog_get_dev: the size query (status and value_off given, asserted equal to the filling
+    call's), then the filling call into outputs between guard bytes, `values` at byte shift dshift.
+    cut: bytes taken off values_cap -- the call must then fail, write the size and leave every
+    output as it was.  -> (status, values, value_off, value_bytes)"""
+    import torch
+    from velarixdb_amd._lib import VBF_EINVAL, lib
+    vo = np.ascontiguousarray(vo, np.uint32)
+    n = vo.size
+    keep = [_up(vo)]
+    if found is not None:
+        keep.append(_up(np.ascontiguousarray(found, np.uint8)))
+    pf = keep[-1][1] if found is not None else None
+    pk = po = None
+    if keys is not None:
+        kb, off = pack_keys(keys, lead, stride)
+        keep.append(_up(kb))
+        pk = keep[-1][1]
+        if off is not None:
+            keep.append(_up(off))
+            po = keep[-1][1]
+    head = (h, keep[0][1], pf, n, pk, po, stride or 0)
+    sp = _stream()
+    ts, ps = _out(n)
+    to, pof = _out((n + 1) * 8)
+    vb = ctypes.c_uint64(77)
+    rc = lib.vbf_vlog_get_dev(*head, ps, None, 0, pof, ctypes.byref(vb), sp)
+    torch.cuda.synchronize()
+    assert rc == 0, lib.vbf_last_error()
+    total = vb.value
+    q_status, q_off = _down(ts, n, np.uint8), _down(to, (n + 1) * 8, np.uint64)
+    ts, ps = _out(n)
+    to, pof = _out((n + 1) * 8)
+    tv, pv = _out(total, dshift)
+    vb = ctypes.c_uint64(77)
+    rc = lib.vbf_vlog_get_dev(*head, ps, pv, total - (cut or 0), pof, ctypes.byref(vb), sp)
+    torch.cuda.synchronize()
+    assert vb.value == total, "the size query and the filling call disagree"
+    if cut:
+        assert rc == VBF_EINVAL and b"values_cap" in lib.vbf_last_error()
+        for t in (ts, to, tv):
+            assert (t.cpu().numpy() == GUARD).all(), "an output was written despite a small capacity"
+        return None
+    assert rc == 0, lib.vbf_last_error()
+    status, voff = _down(ts, n, np.uint8), _down(to, (n + 1) * 8, np.uint64)
+    assert np.array_equal(status, q_status) and np.array_equal(voff, q_off)
+    return status, _down(tv, total, np.uint8, dshift), voff, total
+
+
+def get_host(h, vo, found=None, keys=None, lead=0, stride=None, cut=None):
+    """The same through vbf_vlog_get_host, on numpy buffers with guard bytes."""
+    from velarixdb_amd._lib import VBF_EINVAL, lib
+    vo = np.ascontiguousarray(vo, np.uint32)
+    n = vo.size
+    fd = None if found is None else np.ascontiguousarray(found, np.uint8)
+    pk = po = None
+    if keys is not None:
+        kb, off = pack_keys(keys, lead, stride)
+        pk, po = kb.ctypes.data, (None if off is None else off.ctypes.data)
+    head = (h, vo.ctypes.data, None if fd is None else fd.ctypes.data, n, pk, po, stride or 0)
+    vb = ctypes.c_uint64(77)
+    rc = lib.vbf_vlog_get_host(*head, None, None, 0, None, ctypes.byref(vb))
+    assert rc == 0, lib.vbf_last_error()
+    total = vb.value
+    sizes = (n, total, (n + 1) * 8)
+    outs = [np.full(PAD + s + PAD, GUARD, np.uint8) for s in sizes]
+    p = [o.ctypes.data + PAD for o in outs]
+    vb = ctypes.c_uint64(77)
+    rc = lib.vbf_vlog_get_host(*head, p[0], p[1], total - (cut or 0), p[2], ctypes.byref(vb))
+    assert vb.value == total, "the size query and the filling call disagree"
+    if cut:
+        assert rc == VBF_EINVAL and b"values_cap" in lib.vbf_last_error()
+        assert all((o == GUARD).all() for o in outs), "an output was written despite a small capacity"
+        return None
+    assert rc == 0, lib.vbf_last_error()
+    for o, s in zip(outs, sizes):
+        assert (o[:PAD] == GUARD).all() and (o[PAD + s:] == GUARD).all(), "wrote outside the output"
+    return (outs[0][PAD:PAD + n].copy(), outs[1][PAD:PAD + total].copy(),
+            outs[2][PAD:PAD + sizes[2]].copy().view(np.uint64), total)
+
+
+def same(got, want, what=""):
+    status, values, voff, total = got
+    w_status, w_values, w_voff = want
+    for g, w, name in ((status, w_status, "status"), (voff, w_voff, "value_off"), (values, w_values, "values")):
+        assert g.size == w.size, "%s %s holds %d items, the checker %d" % (what, name, g.size, w.size)
+        bad = np.flatnonzero(g != w)
+        assert bad.size == 0, "%s %s differs at %d of %d items, first %d: got %d want %d" % (
+            what, name, bad.size, g.size, bad[0], g[bad[0]], w[bad[0]])
+    assert total == w_values.size == int(w_voff[-1])
+
+
+def both(L, vo, found=None, keys=None, shifts=SHIFTS, **kw):
+    """_host, and _dev on the log at every byte shift (the values' destination shifted along),
+    against the checker; -> the checker's arrays."""
+    want = vr.get_many(L.log, vo, L.base, found, keys)
+    same(get_host(L.host, vo, found, keys, **kw), want, "host")
+    for j, shift in enumerate(SHIFTS):
+        if shift in shifts:
+            same(get_dev(L.dev[j], vo, found, keys, dshift=(0, 9, 15)[j], **kw), want, "dev shift %d" % shift)
+    return want
+
+
+# ---- 1. the reference's fixture -------------------------------------------------------------
+
+def fixture_log():
+    with open(os.path.join(GOLDEN, "vlog_fixture", "val_log_prefix.bin"), "rb") as f:
+        return f.read()
+
+
+def test_fixture_get_values_and_scan_values(vbf, ora):
+    from velarixdb_amd import Table, ValueLog, get_values, scan_values
+    from velarixdb_amd.vlog import KEY_MISMATCH, SKIPPED, VALUE
+    name = "sstable_1720785462309"
+    log = fixture_log()
+    s = ref.Sst(*sc.read_fixture(name))
+    keys = sorted(s.starts) + [b"zz-absent-%03d" % j for j in range(50)]
+    assert len(keys) == 2844 + 50
+    head = keys.index(b"head")
+    with Table.open_dir(os.path.join(sc.SST, name)) as tab, ValueLog.open(log) as vl:
+        assert (vl.nbytes, vl.base, vl.device) == (76784, 0, 0)
+        found, _, vo, _ = ref.search_many(keys, [s])
+        assert (found[:2844] == 1).all() and not found[2844:].any()
+        plain = vr.get_many(log, vo, 0, found)
+        res, vals = get_values(keys, [tab], vl)
+        assert np.array_equal(res.found, found) and np.array_equal(res.val_offsets, vo)
+        same((vals.status, vals.values, vals.value_off, vals.values.size), plain)
+        assert vals.value(head) == b"6YLW8" and vals.status[head] == VALUE
+        assert (vals.status[2844:] == SKIPPED).all() and vals.value(2844) is None
+        checked = vr.get_many(log, vo, 0, found, keys)
+        res, vals = get_values(keys, [tab], vl, check_keys=True)
+        same((vals.status, vals.values, vals.value_off, vals.values.size), checked)
+        assert vals.status[head] == KEY_MISMATCH and vals.value(head) is None
+        others = np.arange(len(keys)) != head
+        assert np.array_equal(vals.status[others], plain[0][others])  # every other item unchanged
+        # four ranges of the same table, against the checker over the scan checker's listing
+        import sst_scan_ref as scan_ref
+        ks = sorted(s.starts)
+        ranges = [sc.FULL, (ks[100], ks[400]), (b"head", b"head"), (ks[2000], ks[1000])]
+        for check in (False, True):
+            want = scan_ref.scan_many(ranges, [s], 0)
+            r, v = scan_values(ranges, [tab], vl, check_keys=check)
+            assert np.array_equal(r.range_off, want[0]) and np.array_equal(r.val_offsets, want[4])
+            listed = [want[1][int(a):int(b)].tobytes() for a, b in zip(want[2][:-1], want[2][1:])]
+            same((v.status, v.values, v.value_off, v.values.size),
+                 vr.get_many(log, want[4], 0, None, listed if check else None))
+            assert r.range_off.tolist() == [0, 2844, 2844 + 301, 2844 + 302, 2844 + 302]
+            assert v.status[2844 + 301] == (KEY_MISMATCH if check else VALUE)
+    # the raw entry points on the same batch, the log at every byte shift
+    with Logs(log) as L:
+        both(L, vo, found)
+        both(L, vo, found, keys, lead=5)
+
+
+# ---- 2. lengths -----------------------------------------------------------------------------
+
+VALUE_LENGTHS = [0, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 255, 256, 257] + \
+    [2**p + d for p in range(10, 18) for d in (-1, 0, 1)] + [300001]
+KEY_LENGTHS = [0, 1, 3, 4, 5, 8, 17, 4079]
+
+
+@functools.lru_cache(maxsize=None)
+def length_entries():
+    """[(key, value, created, tombstone)]: every value length above, the key lengths in rotation,
+    then 16 short entries behind keys of 0..15 bytes so that the value sources cover every residue."""
+    rng = np.random.default_rng(0x7106)
+    out = []
+    for j, vl in enumerate(VALUE_LENGTHS):
+        out.append((rng.bytes(KEY_LENGTHS[j % len(KEY_LENGTHS)]), rng.bytes(vl), T0 + j, 0))
+    for kl in range(16):
+        out.append((rng.bytes(kl), rng.bytes(33), T0 + 100 + kl, 0))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def length_log():
+    return vr.encode(length_entries(), base=0)
+
+
+def test_lengths(vbf):
+    entries = length_entries()
+    log, offs = length_log()
+    assert {len(k) for k, *_ in entries} >= set(KEY_LENGTHS)
+    assert {(o + 17 + len(k)) % 16 for o, (k, *_) in zip(offs, entries)} == set(range(16))
+    # slice edges of the balanced copy: values end before, at and after a multiple of the slice
+    assert {SLICE - 1, SLICE, SLICE + 1} <= set(VALUE_LENGTHS) and max(VALUE_LENGTHS) > 16 * SLICE
+    keys = [k for k, *_ in entries]
+    n = len(offs)
+    rng = np.random.default_rng(0x9E7)
+    perm = rng.permutation(n)
+    thrice = [j for i in range(n) for j in ([i] * 3 if i % 3 == 0 else [i])]
+    with Logs(log) as L:
+        for order, shifts in ((np.arange(n), SHIFTS), (perm, SHIFTS), (np.array(thrice), (1,))):
+            vo = np.array(offs, np.uint32)[order]
+            want = both(L, vo, shifts=shifts)
+            assert (want[0] == vr.VALUE).all() and np.array_equal(np.diff(want[2]), [len(entries[i][1]) for i in order])
+            both(L, vo, keys=[keys[i] for i in order], lead=3, shifts=(7,))
+        # one item per call (n == 1): the empty value, a one-byte one, the slice-sized one, the last
+        for j in (0, 1, VALUE_LENGTHS.index(SLICE), n - 1):
+            both(L, [offs[j]], shifts=(1,))
+
+
+# ---- 3. window edges ------------------------------------------------------------------------
+
+def test_window_edges(vbf):
+    import struct
+    base = 1000
+    tomb_bytes = (0, 1, 2, 255, 0, 1)  # only byte == 1 is a tombstone
+    entries = [(b"k%d" % j, b"value-%d" % j * (j + 1), T0 + j, t == 1) for j, t in enumerate(tomb_bytes)]
+    log, offs = vr.encode(entries, base)
+    log = bytearray(log)
+    for o, t in zip(offs, tomb_bytes):  # the checker's encoder writes 0 or 1: the other bytes by hand
+        log[o - base + 16] = t
+    log = bytes(log)
+    end = base + len(log)
+    # a whole header whose val_len overruns the end by one byte, and one with both lengths 0xFFFFFFFF
+    over = struct.pack("<IIQB", 2, 4, T0, 0) + b"ab" + b"xyz"
+    huge = struct.pack("<IIQB", 0xFFFFFFFF, 0xFFFFFFFF, T0, 0) + b"ab" + b"xyz"
+    with Logs(log, base) as L:
+        assert offs[-1] + 17 + len(entries[-1][0]) + len(entries[-1][1]) == end  # the last entry ends at base + len
+        vo = offs + [end, 0xFFFFFFFF, end - 1, base - 1, 0, end - 16, offs[0]]
+        want = both(L, vo)
+        assert want[0].tolist() == [1, 2, 1, 1, 1, 2] + [3, 3, 4, 4, 4, 4, 1]
+        keys = [k for k, *_ in entries] + [b"x"] * 6 + [b"k1"]
+        want = both(L, vo, keys=keys, lead=2)
+        assert want[0].tolist() == [1, 2, 1, 1, 1, 2] + [3, 3, 4, 4, 4, 4, 5]
+        # a found mask of 0, 1 and 2, passed straight through
+        found = np.array([1, 1, 2, 0, 1, 2] + [1, 0, 1, 2, 1, 1, 1], np.uint8)
+        want = both(L, vo, found)
+        assert want[0].tolist() == [1, 2, 0, 0, 1, 0] + [3, 0, 4, 0, 4, 4, 1]
+        # all items skipped: value_bytes == 0
+        want = both(L, vo, np.zeros(len(vo), np.uint8))
+        assert not want[0].any() and want[1].size == 0 and not want[2].any()
+        for j in range(len(vo)):  # n == 1
+            both(L, vo[j:j + 1], shifts=(7,))
+    for tail in (over, huge):
+        bad = log + tail
+        with Logs(bad, base) as L:
+            want = both(L, offs + [end], keys=None)
+            assert want[0].tolist() == [1, 2, 1, 1, 1, 2, 4]
+    with Logs(log + over + b"!", base) as L:  # one more byte and the same entry is whole
+        assert both(L, [end])[1].tobytes() == b"xyz!"
+    with Logs(b"", 500) as L:  # an empty window: everything at or past its end is NONE, the rest BAD
+        assert both(L, [0, 499, 500, 501])[0].tolist() == [4, 4, 3, 3]
+
+
+# ---- 4. capacity ----------------------------------------------------------------------------
+
+def test_capacity(vbf):
+    log, offs = length_log()
+    vo = np.array(offs[:20], np.uint32)
+    with Logs(log) as L:
+        want = vr.get_many(log, vo)
+        same(get_host(L.host, vo), want)          # the size query, then the exact capacity
+        same(get_dev(L.dev[1], vo), want)
+        assert get_host(L.host, vo, cut=1) is None  # one byte short: VBF_EINVAL, the size written, no output touched
+        assert get_dev(L.dev[1], vo, cut=1) is None
+        same(get_dev(L.dev[1], vo), want)          # the stream and the workspaces are fine afterwards
+
+
+# ---- 5. encode ------------------------------------------------------------------------------
+
+def enc_inputs(entries, lead, vlead, stride=None):
+    keys, offs = pack_keys([k for k, *_ in entries], lead, stride)
+    vals, voff = pack_keys([v for _, v, *_ in entries], vlead)
+    cr = np.array([c for *_, c, _ in entries], np.int64)
+    tb = np.array([t for *_, t in entries], np.uint8)
+    return keys, offs, vals, voff, cr, tb
+
+
+def encode_dev(entries, base=0, lead=0, vlead=0, stride=None, meta=True, cut=0, dshift=0):
+    """vbf_vlog_encode_dev: the size query, then the filling call between guard bytes.
+    -> (log bytes, val_offsets) or None for a capacity `cut` short (checked untouched)."""
+    import torch
+    from velarixdb_amd._lib import VBF_EINVAL, lib
+    n = len(entries)
+    keys, offs, vals, voff, cr, tb = enc_inputs(entries, lead, vlead, stride)
+    keep = [_up(keys, 3), _up(offs) if offs is not None else (None, None), _up(vals, 5), _up(voff), _up(cr), _up(tb)]
+    p = [q for _, q in keep]
+    head = (p[0], p[1], stride or 0, n, p[2], p[3], p[4] if meta else None, p[5] if meta else None, base)
+    sp = _stream()
+    ln = ctypes.c_uint64(77)
+    rc = lib.vbf_vlog_encode_dev(*head, None, 0, ctypes.byref(ln), None, sp)
+    assert rc == 0, lib.vbf_last_error()
+    total = ln.value
+    to, po = _out(total, dshift)
+    tv, pv = _out(4 * n)
+    ln = ctypes.c_uint64(77)
+    rc = lib.vbf_vlog_encode_dev(*head, po, total - cut, ctypes.byref(ln), pv, sp)
+    torch.cuda.synchronize()
+    assert ln.value == total
+    if cut:
+        assert rc == VBF_EINVAL and b"out_cap" in lib.vbf_last_error()
+        assert (to.cpu().numpy() == GUARD).all() and (tv.cpu().numpy() == GUARD).all()
+        return None
+    assert rc == 0, lib.vbf_last_error()
+    return _down(to, total, np.uint8, dshift).tobytes(), _down(tv, 4 * n, np.uint32)
+
+
+def encode_host(entries, base=0, lead=0, vlead=0, stride=None, meta=True, cut=0):
+    from velarixdb_amd._lib import VBF_EINVAL, lib
+    n = len(entries)
+    keys, offs, vals, voff, cr, tb = enc_inputs(entries, lead, vlead, stride)
+    head = (keys.ctypes.data, None if offs is None else offs.ctypes.data, stride or 0, n, vals.ctypes.data,
+            voff.ctypes.data, cr.ctypes.data if meta else None, tb.ctypes.data if meta else None, base)
+    ln = ctypes.c_uint64(77)
+    rc = lib.vbf_vlog_encode_host(*head, None, 0, ctypes.byref(ln), None, 0)
+    assert rc == 0, lib.vbf_last_error()
+    total = ln.value
+    out, vo = np.full(PAD + total + PAD, GUARD, np.uint8), np.full(PAD + 4 * n + PAD, GUARD, np.uint8)
+    ln = ctypes.c_uint64(77)
+    rc = lib.vbf_vlog_encode_host(*head, out.ctypes.data + PAD, total - cut, ctypes.byref(ln), vo.ctypes.data + PAD, 0)
+    assert ln.value == total
+    if cut:
+        assert rc == VBF_EINVAL and b"out_cap" in lib.vbf_last_error()
+        assert (out == GUARD).all() and (vo == GUARD).all()
+        return None
+    assert rc == 0, lib.vbf_last_error()
+    for o, s in ((out, total), (vo, 4 * n)):
+        assert (o[:PAD] == GUARD).all() and (o[PAD + s:] == GUARD).all(), "wrote outside the output"
+    return out[PAD:PAD + total].tobytes(), vo[PAD:PAD + 4 * n].copy().view(np.uint32)
+
+
+def test_encode(vbf):
+    import torch
+    from velarixdb_amd import ValueLog
+    from velarixdb_amd._lib import VBF_EINVAL, lib
+    entries = [(k, v, c, (0, 1, 2, 255)[j % 4]) for j, (k, v, c, _) in enumerate(length_entries())]
+    n = len(entries)
+    for base in (0, 1000):
+        want, woffs = vr.encode(entries, base)
+        for lead, vlead in ((0, 0), (29, 11)):  # offsets[0] != 0 and value_off[0] != 0
+            for j, fn in enumerate((encode_host, encode_dev, encode_dev)):
+                kw = {"dshift": (0, 0, 13)[j]} if fn is encode_dev else {}
+                got, vo = fn(entries, base, lead, vlead, **kw)
+                assert got == want, "%s: the log differs at byte %d" % (fn.__name__, next(
+                    i for i in range(min(len(got), len(want)) + 1) if got[i:i + 1] != want[i:i + 1]))
+                assert vo.tolist() == woffs
+    # a fixed stride, and NULL created_ms / tombstones (zeros are written)
+    rng = np.random.default_rng(0x57D)
+    fixed = [(rng.bytes(24), rng.bytes(int(rng.integers(0, 200))), T0 + j, j % 3 == 0) for j in range(500)]
+    for meta in (True, False):
+        want, woffs = vr.encode(fixed if meta else [(k, v, 0, 0) for k, v, *_ in fixed], 77)
+        for fn in (encode_host, encode_dev):
+            got, vo = fn(fixed, 77, stride=24, meta=meta)
+            assert got == want and vo.tolist() == woffs
+    # the capacity one short (the size query and the exact capacity ran above)
+    assert encode_host(fixed, 77, cut=1) is None and encode_dev(fixed, 77, cut=1) is None
+    # a descending value_off, seen by the first pass on the device and by the host loop
+    keys, offs, vals, voff, cr, tb = enc_inputs(fixed[:10], 0, 0)
+    voff = voff.copy()
+    voff[4], voff[5] = voff[5], voff[4]
+    ln = ctypes.c_uint64(7)
+    rc = lib.vbf_vlog_encode_host(keys.ctypes.data, offs.ctypes.data, 0, 10, vals.ctypes.data, voff.ctypes.data, None,
+                                  None, 0, None, 0, ctypes.byref(ln), None, 0)
+    assert rc == VBF_EINVAL and b"descend at entry 4" in lib.vbf_last_error() and ln.value == 0
+    keep = [_up(a) for a in (keys, offs, vals, voff)]
+    p = [q for _, q in keep]
+    ln = ctypes.c_uint64(7)
+    rc = lib.vbf_vlog_encode_dev(p[0], p[1], 0, 10, p[2], p[3], None, None, 0, None, 0, ctypes.byref(ln), None, _stream())
+    assert rc == VBF_EINVAL and b"descend at entry 4" in lib.vbf_last_error() and ln.value == 0
+    torch.cuda.synchronize()
+    # the Python layer, and what it wrote read back through it
+    put = entries[:60]
+    log, vo = ValueLog.encode([k for k, *_ in put], [v for _, v, *_ in put], [c for *_, c, _ in put],
+                              [t for *_, t in put], base=1000)
+    want, woffs = vr.encode(put, 1000)
+    assert log == want and vo.tolist() == woffs
+    with ValueLog.open(log, base=1000) as vl:
+        got = vl.get_many(vo, keys=[k for k, *_ in put])
+        for j, (k, v, c, t) in enumerate(put):
+            assert got.value(j) == (None if t else v)  # a byte != 0 was written as 1
+
+
+# ---- 6. the chain on one stream -------------------------------------------------------------
+
+def test_put_then_get_chain_on_one_stream(vbf):
+    """vbf_vlog_encode_dev -> vbf_sst_encode_dev fed with its val_offsets -> vbf_table_open_dev and
+    vbf_vlog_open_dev on those buffers -> vbf_table_get_dev -> vbf_vlog_get_dev fed with its found and
+    val_offsets device arrays.  No array comes to the host in between (sizes do)."""
+    import torch
+    from velarixdb_amd._lib import call, lib
+    rng = np.random.default_rng(0xC4A1)
+    keys = sorted({rng.bytes(int(rng.integers(1, 40))) for _ in range(3000)})
+    n = len(keys)
+    values = [rng.bytes(int(rng.integers(0, 700))) for _ in range(n)]
+    tomb = (np.arange(n) % 11 == 0).astype(np.uint8)
+    created = (T0 + np.arange(n)).astype(np.int64)
+    base = 4321
+    kb, koff = pack_keys(keys)
+    vb, voff = pack_keys(values)
+    keep = [_up(a) for a in (kb, koff, vb, voff, created, tomb)]
+    pk, pko, pv, pvo, pcr, ptb = [q for _, q in keep]
+    sp = _stream()
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    ln = ctypes.c_uint64()
+    call("vbf_vlog_encode_dev", pk, pko, 0, n, pv, pvo, pcr, ptb, base, None, 0, ctypes.byref(ln), None, sp)
+    t_log = torch.zeros(ln.value, dtype=torch.uint8, device="cuda:0")
+    t_vo = torch.zeros(n, dtype=torch.int32, device="cuda:0")
+    call("vbf_vlog_encode_dev", pk, pko, 0, n, pv, pvo, pcr, ptb, base, P(t_log), ln.value, ctypes.byref(ln), P(t_vo), sp)
+    dl, il, nb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    S = (ctypes.byref(dl), ctypes.byref(il), ctypes.byref(nb))
+    call("vbf_sst_encode_dev", pk, pko, 0, n, P(t_vo), pcr, ptb, None, 0, S[0], None, 0, S[1], None, 0, S[2], sp)
+    td = torch.zeros(dl.value, dtype=torch.uint8, device="cuda:0")
+    ti = torch.zeros(il.value, dtype=torch.uint8, device="cuda:0")
+    tblk = torch.zeros(nb.value, dtype=torch.int32, device="cuda:0")
+    call("vbf_sst_encode_dev", pk, pko, 0, n, P(t_vo), pcr, ptb, P(td), dl.value, S[0], P(ti), il.value, S[1], P(tblk),
+         nb.value, S[2], sp)
+    ht, hv = ctypes.c_void_p(), ctypes.c_void_p()
+    call("vbf_table_open_dev", P(td), dl.value, P(ti), il.value, P(tblk), nb.value, sp, ctypes.byref(ht))
+    call("vbf_vlog_open_dev", P(t_log), ln.value, base, ctypes.byref(hv))
+    try:
+        ask = keys[::2] + [k + b"\0absent" for k in keys[:100]]
+        m = len(ask)
+        qb, qoff = pack_keys(ask)
+        tq, pq = _up(qb)
+        tqo, pqo = _up(qoff)
+        t_found = torch.zeros(m, dtype=torch.uint8, device="cuda:0")
+        t_val = torch.zeros(m, dtype=torch.int32, device="cuda:0")
+        th = (ctypes.c_void_p * 1)(ht.value)
+        call("vbf_table_get_dev", pq, pqo, 0, m, 1, th, None, P(t_found), None, P(t_val), None, sp)
+        ts, ps = _out(m)
+        to, po = _out((m + 1) * 8)
+        tot = ctypes.c_uint64()
+        call("vbf_vlog_get_dev", hv, P(t_val), P(t_found), m, pq, pqo, 0, ps, None, 0, po, ctypes.byref(tot), sp)
+        tv, pvv = _out(tot.value)
+        call("vbf_vlog_get_dev", hv, P(t_val), P(t_found), m, pq, pqo, 0, ps, pvv, tot.value, po, ctypes.byref(tot), sp)
+        torch.cuda.synchronize()
+        status, voff_out = _down(ts, m, np.uint8), _down(to, (m + 1) * 8, np.uint64)
+        vals = _down(tv, tot.value, np.uint8).tobytes()
+        at = {k: j for j, k in enumerate(keys)}
+        for j, k in enumerate(ask):
+            got = vals[int(voff_out[j]):int(voff_out[j + 1])]
+            if k not in at:
+                assert status[j] == vr.SKIPPED and got == b""
+            elif tomb[at[k]]:
+                assert status[j] == vr.SKIPPED and got == b""  # found == 2: the table already says tombstone
+            else:
+                assert status[j] == vr.VALUE and got == values[at[k]], j
+        # the log itself is the checker's
+        want, woffs = vr.encode(list(zip(keys, values, created.tolist(), tomb.tolist())), base)
+        assert t_log.cpu().numpy().tobytes() == want and t_vo.cpu().numpy().view(np.uint32).tolist() == woffs
+    finally:
+        lib.vbf_table_free(ht)
+        lib.vbf_vlog_free(hv)

@@ -9,7 +9,8 @@ from ._lib import LIB_PATH, VbfError, device_count, lib  # noqa: F401
 from .filter import (DEFAULT_FALSE_POSITIVE_RATE, FILTER_FILE_NAME, HOST, BloomFilter,  # noqa: F401
                      num_bits, num_hash_functions)
 from .keys import HostBatch, I32Vec, RawMessage, Usize, pack, pack_fixed, pack_offsets  # noqa: F401
-from .table import GetResult, ScanResult, Table, get_many, scan_many  # noqa: F401
-from . import compaction, key_range, sst, table  # noqa: F401
+from .table import GetResult, ScanResult, Table, get_many, get_values, scan_many, scan_values  # noqa: F401
+from .vlog import ValueLog, Values  # noqa: F401
+from . import compaction, key_range, sst, table, vlog  # noqa: F401
 
 __version__ = "0.1.0"

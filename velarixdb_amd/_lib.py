@@ -26,6 +26,9 @@ VBF_BUILD_ATOMIC = 1
 VBF_BUILD_PARTITIONED = 2
 VBF_BUILD_FRESH = 0x100  # OR into a build strategy: BloomFilter::new fused with the build (vbf.h)
 VBF_SCAN_KEEP_TOMBSTONES, VBF_SCAN_END_EXCLUSIVE = 1, 2  # vbf_table_scan_* flags
+# vbf_vlog_get_* status
+(VBF_VLOG_SKIPPED, VBF_VLOG_VALUE, VBF_VLOG_TOMBSTONE, VBF_VLOG_NONE, VBF_VLOG_BAD,
+ VBF_VLOG_KEY_MISMATCH) = range(6)
 
 _u8p = ctypes.c_void_p  # raw pointers (host or device) travel as integers
 _u64 = ctypes.c_uint64
@@ -133,6 +136,18 @@ SIGNATURES = {
                                    ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp]),
     "vbf_table_scan_host": (_int, [_vp, _vp, _u64, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64,
                                     ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "vbf_vlog_open_dev": (_int, [_vp, _u64, _u64, ctypes.POINTER(_vp)]),
+    "vbf_vlog_open_host": (_int, [_vp, _u64, _u64, _int, ctypes.POINTER(_vp)]),
+    "vbf_vlog_free": (None, [_vp]),
+    "vbf_vlog_bytes": (_u64, [_vp]),
+    "vbf_vlog_base": (_u64, [_vp]),
+    "vbf_vlog_device": (_int, [_vp]),
+    "vbf_vlog_get_dev": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64), _vp]),
+    "vbf_vlog_get_host": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64)]),
+    "vbf_vlog_encode_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64),
+                                    _vp, _vp]),
+    "vbf_vlog_encode_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64),
+                                     _vp, _int]),
 }
 
 
@@ -185,7 +200,8 @@ def device_count():
 
 PHASES = ("tile_sort", "transpose", "seg_or", "atomic_build", "probe", "sst_walk", "sst_scan", "sst_emit",
           "merge_levels", "fold", "select", "probe_pack", "probe_seg", "probe_out", "enc_tile", "enc_scan",
-          "enc_index", "enc_data", "table_open", "table_get", "scan_rank", "scan_emit")
+          "enc_index", "enc_data", "table_open", "table_get", "scan_rank", "scan_emit", "vlog_sizes", "vlog_copy",
+          "vlog_encode")
 
 
 def profile_read():

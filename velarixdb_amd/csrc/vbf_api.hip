@@ -169,6 +169,11 @@ enum WsSlot {
     kWsTableScanPairs = 18,
     kWsTableScan = 19,
     kWsTableScanIO = 20,
+    kWsVlog = 21,
+    kWsVlogIO = 22,
+    kWsVlogOut = 23,
+    kWsVlogEnc = 24,
+    kWsVlogEncIO = 25,
 };
 struct Workspace {
     int device;
@@ -3860,6 +3865,393 @@ int vbf_table_scan_host(const uint8_t* bounds, const uint64_t* bounds_off, uint6
     } catch (const std::bad_alloc&) {
         return table_no_memory();
     }
+    return ok();
+}
+
+}  // extern "C"
+
+// ---- value-log reads and appends (ValueLog::get / ValueLog::append) ----
+
+// A device-resident window of the value log: the file's bytes [base, base + len), borrowed from the
+// caller or uploaded into `owned`.  Immutable once opened; the log has no index, so nothing is parsed.
+struct vbf_vlog {
+    int device = 0;
+    uint64_t len = 0, base = 0;
+    const uint8_t* bytes = nullptr;
+    void* owned = nullptr;
+    ~vbf_vlog() {
+        if (!owned || hip_forked()) return;  // a forked child: the parent's allocation
+        int prev = -1;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(device);
+        (void)hipFree(owned);
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+namespace {
+
+int vlog_open_check(const uint8_t* bytes, uint64_t len, uint64_t base, vbf_vlog** out) {
+    if (!out) return fail(VBF_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (len && !bytes) return fail(VBF_EINVAL, "bytes is NULL");
+    if (base + len < base)
+        return fail(VBF_EINVAL, "base %llu + len %llu wraps", (unsigned long long)base, (unsigned long long)len);
+    return VBF_OK;
+}
+
+// The argument checks of vbf_vlog_get_* that need no HIP call.
+int vlog_get_check(const vbf_vlog* v, const uint32_t* val_offsets, uint64_t n, uint64_t* value_bytes) {
+    if (!value_bytes) return fail(VBF_EINVAL, "value_bytes is NULL");
+    *value_bytes = 0;
+    if (!v) return fail(VBF_EINVAL, "vlog is NULL");
+    if (n && !val_offsets) return fail(VBF_EINVAL, "val_offsets is NULL");
+    if (n > 0x7FFFFFFEull)  // the lengths' scan runs over n + 1 items
+        return fail(VBF_EINVAL, "too many items: %llu (limit 2^31 - 2)", (unsigned long long)n);
+    return VBF_OK;
+}
+
+// Sizes pass and scan on the log's device (every pointer there): status, lengths and positions into
+// the stream's workspace, the byte total read back (one stream synchronisation).  `a` comes back
+// ready for vlog_get_fill.  Workspace: 25 bytes per item plus the scan's scratch.
+int vlog_get_sizes(const vbf_vlog* v, const uint32_t* val_offsets, const uint8_t* found, uint64_t n,
+                   const uint8_t* keys, const uint64_t* offsets, uint64_t stride, hipStream_t s, vbf::VlogGetArgs* a,
+                   uint64_t* total) {
+    *a = vbf::VlogGetArgs{};
+    a->bytes = v->bytes;
+    a->len = v->len;
+    a->base = v->base;
+    a->val_offsets = val_offsets;
+    a->found = found;
+    a->n = n;
+    a->keys = keys;
+    a->offsets = keys ? offsets : nullptr;
+    a->stride = stride;
+    size_t tmpb = 0;
+    HIP_TRY(vbf::scan_u64(nullptr, &tmpb, nullptr, nullptr, n + 1, s));
+    const uint64_t o_len = align256(n), o_voff = o_len + align256((n + 1) * 8);
+    const uint64_t o_src = o_voff + align256((n + 1) * 8), o_tmp = o_src + align256(n * 8);
+    void* ws = nullptr;
+    int rc = get_workspace(s, o_tmp + tmpb, &ws, kWsVlog);
+    if (rc) return rc;
+    char* b = static_cast<char*>(ws);
+    a->status = reinterpret_cast<uint8_t*>(b);
+    a->vlen = reinterpret_cast<uint64_t*>(b + o_len);
+    uint64_t* voff = reinterpret_cast<uint64_t*>(b + o_voff);
+    a->voff = voff;
+    a->src = reinterpret_cast<uint64_t*>(b + o_src);
+    HIP_TRY(hipMemsetAsync(a->vlen + n, 0, 8, s));
+    vbf::phase_begin(vbf::kPhaseVlogSizes, s);
+    HIP_TRY(vbf::vlog_sizes(*a, s));
+    HIP_TRY(vbf::scan_u64(b + o_tmp, &tmpb, a->vlen, voff, n + 1, s));
+    vbf::phase_end(vbf::kPhaseVlogSizes, s);
+    HIP_TRY(hipMemcpyAsync(total, voff + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    a->total = *total;
+    return VBF_OK;
+}
+
+int vlog_values_cap(const uint8_t* values, uint64_t values_cap, uint64_t total) {
+    if (values && values_cap < total)
+        return fail(VBF_EINVAL, "values_cap %llu < %llu value bytes", (unsigned long long)values_cap,
+                    (unsigned long long)total);
+    return VBF_OK;
+}
+
+// The copy pass, queued on `s` (values on the device).
+int vlog_get_fill(vbf::VlogGetArgs a, uint8_t* values, hipStream_t s) {
+    a.values = values;
+    vbf::phase_begin(vbf::kPhaseVlogCopy, s);
+    HIP_TRY(vbf::vlog_copy(a, s));
+    vbf::phase_end(vbf::kPhaseVlogCopy, s);
+    return VBF_OK;
+}
+
+constexpr uint64_t kVlogMaxOffset = 1ull << 32;  // data.db stores the value offset as u32
+
+// The argument checks of vbf_vlog_encode_* that need no HIP call.
+int vlog_enc_check_args(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                        const uint64_t* value_off, uint64_t base, uint64_t* out_len) {
+    if (!out_len) return fail(VBF_EINVAL, "out_len is NULL");
+    *out_len = 0;
+    if (!n) return VBF_OK;
+    if (!value_off) return fail(VBF_EINVAL, "value_off is NULL");
+    if (!keys && !offsets && stride) return fail(VBF_EINVAL, "keys is NULL");
+    if (!offsets && stride > 0xFFFFFFFFull)
+        return fail(VBF_EINVAL, "key of %llu bytes: key_len is a u32", (unsigned long long)stride);
+    // an entry is at least its 17-byte header: decidable before the lengths are known
+    if (n > kVlogMaxOffset / 17 + 1 || base + 17 * (n - 1) >= kVlogMaxOffset)
+        return fail(VBF_EINVAL, "entry %llu would start at or beyond 2^32: data.db's u32 value offset cannot address it",
+                    (unsigned long long)(base >= kVlogMaxOffset ? 0 : (kVlogMaxOffset - base + 16) / 17));
+    return VBF_OK;
+}
+
+// The append's sizes from the first, the last-but-one and the last entry of both offset arrays
+// (ko / vo = {[0], [n - 1], [n]}): total bytes, the last entry's start against the 2^32 limit, the
+// capacity rule (too small: VBF_EINVAL with *out_len written and nothing else).
+int vlog_enc_plan(vbf::VlogEncArgs* a, const uint64_t ko[3], const uint64_t vo[3], const uint8_t* out,
+                  uint64_t out_cap, uint64_t* out_len) {
+    const uint64_t n = a->n;
+    a->k0 = ko[0];
+    a->v0 = vo[0];
+    a->k_end = ko[2];
+    a->v_end = vo[2];
+    a->total = 17 * n + (ko[2] - ko[0]) + (vo[2] - vo[0]);
+    const uint64_t last = a->base + 17 * (n - 1) + (ko[1] - ko[0]) + (vo[1] - vo[0]);
+    if (last >= kVlogMaxOffset)
+        return fail(VBF_EINVAL, "the last entry would start at %llu, at or beyond 2^32: data.db's u32 value offset "
+                    "cannot address it", (unsigned long long)last);
+    if (!a->keys && ko[2] > ko[0]) return fail(VBF_EINVAL, "keys is NULL");
+    if (!a->values && vo[2] > vo[0]) return fail(VBF_EINVAL, "values is NULL");
+    *out_len = a->total;
+    if (out && out_cap < a->total)
+        return fail(VBF_EINVAL, "out_cap %llu < %llu log bytes", (unsigned long long)out_cap,
+                    (unsigned long long)a->total);
+    return VBF_OK;
+}
+
+int vlog_enc_emit(const vbf::VlogEncArgs& a, hipStream_t s) {
+    vbf::phase_begin(vbf::kPhaseVlogEncode, s);
+    HIP_TRY(vbf::vlog_encode(a, s));
+    vbf::phase_end(vbf::kPhaseVlogEncode, s);
+    return VBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbf_vlog_open_dev(const uint8_t* bytes, uint64_t len, uint64_t base, vbf_vlog** out) {
+    int rc = vlog_open_check(bytes, len, base, out);
+    if (rc) return rc;
+    FORK_GUARD();
+    std::unique_ptr<vbf_vlog> v(new (std::nothrow) vbf_vlog());
+    if (!v) return table_no_memory();
+    HIP_TRY(hipGetDevice(&v->device));
+    v->len = len;
+    v->base = base;
+    v->bytes = len ? bytes : nullptr;
+    *out = v.release();
+    return ok();
+}
+
+int vbf_vlog_open_host(const uint8_t* bytes, uint64_t len, uint64_t base, int device, vbf_vlog** out) {
+    int rc = vlog_open_check(bytes, len, base, out);
+    if (rc) return rc;
+    std::unique_ptr<vbf_vlog> v(new (std::nothrow) vbf_vlog());
+    if (!v) return table_no_memory();
+    DEVICE_SCOPE(device);
+    v->device = device;
+    v->len = len;
+    v->base = base;
+    if (len) {
+        hipStream_t s;
+        if ((rc = filter_stream(device, &s))) return rc;
+        HostCall turn(device);
+        HIP_TRY(hipMalloc(&v->owned, len));
+        HIP_TRY(hipMemcpyAsync(v->owned, bytes, len, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));  // a pageable source
+        v->bytes = static_cast<const uint8_t*>(v->owned);
+    }
+    *out = v.release();
+    return ok();
+}
+
+void vbf_vlog_free(vbf_vlog* v) { delete v; }
+uint64_t vbf_vlog_bytes(const vbf_vlog* v) { return v ? v->len : 0; }
+uint64_t vbf_vlog_base(const vbf_vlog* v) { return v ? v->base : 0; }
+int vbf_vlog_device(const vbf_vlog* v) { return v ? v->device : VBF_DEVICE_HOST; }
+
+int vbf_vlog_get_dev(const vbf_vlog* v, const uint32_t* val_offsets, const uint8_t* found, uint64_t n,
+                     const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint8_t* status, uint8_t* values,
+                     uint64_t values_cap, uint64_t* value_off, uint64_t* value_bytes, void* stream) {
+    int rc = vlog_get_check(v, val_offsets, n, value_bytes);
+    if (rc) return rc;
+    if (!n) return ok();
+    FORK_GUARD();
+    hipStream_t s = (hipStream_t)stream;
+    int cur = -1;
+    HIP_TRY(hipGetDevice(&cur));
+    if (cur != v->device)
+        return fail(VBF_EINVAL, "the log lives on device %d, the current device is %d", v->device, cur);
+    vbf::VlogGetArgs a;
+    uint64_t total = 0;
+    if ((rc = vlog_get_sizes(v, val_offsets, found, n, keys, offsets, stride, s, &a, &total))) return rc;
+    *value_bytes = total;
+    if ((rc = vlog_values_cap(values, values_cap, total))) return rc;
+    if (status) HIP_TRY(hipMemcpyAsync(status, a.status, n, hipMemcpyDeviceToDevice, s));
+    if (value_off) HIP_TRY(hipMemcpyAsync(value_off, a.voff, (n + 1) * 8, hipMemcpyDeviceToDevice, s));
+    if (values && (rc = vlog_get_fill(a, values, s))) return rc;
+    return ok();
+}
+
+int vbf_vlog_get_host(const vbf_vlog* v, const uint32_t* val_offsets, const uint8_t* found, uint64_t n,
+                      const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint8_t* status, uint8_t* values,
+                      uint64_t values_cap, uint64_t* value_off, uint64_t* value_bytes) {
+    int rc = vlog_get_check(v, val_offsets, n, value_bytes);
+    if (rc) return rc;
+    if (keys && offsets)
+        for (uint64_t j = 0; j < n; ++j)
+            if (offsets[j] > offsets[j + 1])
+                return fail(VBF_EINVAL, "offsets descend at key %llu", (unsigned long long)j);
+    if (!n) {
+        if (value_off) value_off[0] = 0;
+        return ok();
+    }
+    try {
+        const int device = v->device;
+        DEVICE_SCOPE(device);
+        hipStream_t s;
+        if ((rc = filter_stream(device, &s))) return rc;
+        HostCall turn(device);
+        const uint64_t k0 = keys && offsets ? offsets[0] : 0;
+        const uint64_t kb = !keys ? 0 : (offsets ? offsets[n] - k0 : n * stride);
+        const uint64_t o_found = align256(n * 4), o_keys = o_found + align256(found ? n : 0);
+        const uint64_t o_off = o_keys + align256(kb + 1);
+        void* ws = nullptr;
+        if ((rc = get_workspace(s, o_off + (keys && offsets ? (n + 1) * 8 : 0), &ws, kWsVlogIO))) return rc;
+        char* b = static_cast<char*>(ws);
+        std::vector<uint64_t> o;
+        HIP_TRY(hipMemcpyAsync(b, val_offsets, n * 4, hipMemcpyHostToDevice, s));
+        if (found) HIP_TRY(hipMemcpyAsync(b + o_found, found, n, hipMemcpyHostToDevice, s));
+        if (kb) HIP_TRY(hipMemcpyAsync(b + o_keys, keys + k0, kb, hipMemcpyHostToDevice, s));
+        if (keys && offsets) {  // rebased to positions in the device copy
+            o.assign(offsets, offsets + n + 1);
+            for (auto& x : o) x -= k0;
+            HIP_TRY(hipMemcpyAsync(b + o_off, o.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+        }
+        vbf::VlogGetArgs a;
+        uint64_t total = 0;
+        rc = vlog_get_sizes(v, reinterpret_cast<const uint32_t*>(b), found ? reinterpret_cast<const uint8_t*>(b + o_found) : nullptr,
+                            n, keys ? reinterpret_cast<const uint8_t*>(b + o_keys) : nullptr,
+                            keys && offsets ? reinterpret_cast<const uint64_t*>(b + o_off) : nullptr, stride, s, &a, &total);
+        if (rc) {
+            (void)hipStreamSynchronize(s);  // the uploads read the caller's buffers
+            return rc;
+        }
+        *value_bytes = total;
+        if ((rc = vlog_values_cap(values, values_cap, total))) return rc;
+        if (status) HIP_TRY(hipMemcpyAsync(status, a.status, n, hipMemcpyDeviceToHost, s));
+        if (value_off) HIP_TRY(hipMemcpyAsync(value_off, a.voff, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (values && total) {
+            void* d_values = nullptr;
+            if ((rc = get_workspace(s, total, &d_values, kWsVlogOut))) return rc;
+            if ((rc = vlog_get_fill(a, static_cast<uint8_t*>(d_values), s))) return rc;
+            HIP_TRY(hipMemcpyAsync(values, d_values, total, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+int vbf_vlog_encode_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, const uint8_t* values,
+                        const uint64_t* value_off, const int64_t* created_ms, const uint8_t* tombstones, uint64_t base,
+                        uint8_t* out, uint64_t out_cap, uint64_t* out_len, uint32_t* val_offsets, void* stream) {
+    int rc = vlog_enc_check_args(keys, offsets, stride, n, value_off, base, out_len);
+    if (rc) return rc;
+    if (!n) return ok();
+    FORK_GUARD();
+    hipStream_t s = (hipStream_t)stream;
+    void* ws = nullptr;
+    if ((rc = get_workspace(s, 256, &ws, kWsVlogEnc))) return rc;
+    vbf::VlogEncArgs a{};
+    a.keys = keys;
+    a.offsets = offsets;
+    a.stride = stride;
+    a.n = n;
+    a.values = values;
+    a.value_off = value_off;
+    a.created = created_ms;
+    a.tomb = tombstones;
+    a.base = base;
+    a.err = static_cast<uint32_t*>(ws);
+    HIP_TRY(hipMemsetAsync(a.err, 0, 4, s));
+    HIP_TRY(hipMemsetAsync(a.err + 1, 0xFF, 4, s));
+    vbf::phase_begin(vbf::kPhaseVlogEncode, s);
+    HIP_TRY(vbf::vlog_enc_check(a, s));
+    vbf::phase_end(vbf::kPhaseVlogEncode, s);
+    uint64_t ko[3] = {0, (n - 1) * stride, n * stride}, vo[3] = {0, 0, 0};
+    uint32_t ev[2] = {0, 0};
+    if (offsets) {
+        HIP_TRY(hipMemcpyAsync(&ko[0], offsets, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&ko[1], offsets + n - 1, 16, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipMemcpyAsync(&vo[0], value_off, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&vo[1], value_off + n - 1, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ev, a.err, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (ev[0] & vbf::kVlogEncErrOrder) return fail(VBF_EINVAL, "offsets or value_off descend at entry %u", ev[1]);
+    if (ev[0] & vbf::kVlogEncErrLong)
+        return fail(VBF_EINVAL, "entry %u: a key or value longer than 2^32 - 1 bytes (key_len and val_len are u32)", ev[1]);
+    if ((rc = vlog_enc_plan(&a, ko, vo, out, out_cap, out_len))) return rc;
+    a.out = out;
+    a.val_offsets = val_offsets;
+    if ((out || val_offsets) && (rc = vlog_enc_emit(a, s))) return rc;
+    return ok();
+}
+
+int vbf_vlog_encode_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, const uint8_t* values,
+                         const uint64_t* value_off, const int64_t* created_ms, const uint8_t* tombstones, uint64_t base,
+                         uint8_t* out, uint64_t out_cap, uint64_t* out_len, uint32_t* val_offsets, int device) {
+    int rc = vlog_enc_check_args(keys, offsets, stride, n, value_off, base, out_len);
+    if (rc) return rc;
+    if (!n) return ok();
+    for (uint64_t j = 0; j < n; ++j) {
+        if (value_off[j] > value_off[j + 1] || (offsets && offsets[j] > offsets[j + 1]))
+            return fail(VBF_EINVAL, "offsets or value_off descend at entry %llu", (unsigned long long)j);
+        if (value_off[j + 1] - value_off[j] > 0xFFFFFFFFull || (offsets && offsets[j + 1] - offsets[j] > 0xFFFFFFFFull))
+            return fail(VBF_EINVAL, "entry %llu: a key or value longer than 2^32 - 1 bytes (key_len and val_len are u32)",
+                        (unsigned long long)j);
+    }
+    vbf::VlogEncArgs a{};
+    a.keys = keys;  // for the plan's NULL checks; the device pointers follow
+    a.values = values;
+    a.stride = stride;
+    a.n = n;
+    a.base = base;
+    const uint64_t ko[3] = {offsets ? offsets[0] : 0, offsets ? offsets[n - 1] : (n - 1) * stride,
+                            offsets ? offsets[n] : n * stride};
+    const uint64_t vo[3] = {value_off[0], value_off[n - 1], value_off[n]};
+    if ((rc = vlog_enc_plan(&a, ko, vo, out, out_cap, out_len))) return rc;
+    if (!out && !val_offsets) return ok();  // the size query needs no device
+    DEVICE_SCOPE(device);
+    hipStream_t s;
+    if ((rc = filter_stream(device, &s))) return rc;
+    HostCall turn(device);
+    // device image: keys | offsets | values | value_off | created | tombstones | val_offsets | out
+    const uint64_t kb = ko[2] - ko[0], vb = vo[2] - vo[0];
+    const uint64_t o_off = align256(kb), o_val = o_off + align256(offsets ? (n + 1) * 8 : 0);
+    const uint64_t o_voff = o_val + align256(vb), o_cr = o_voff + align256((n + 1) * 8);
+    const uint64_t o_tb = o_cr + align256(created_ms ? n * 8 : 0), o_vo = o_tb + align256(tombstones ? n : 0);
+    const uint64_t o_out = o_vo + align256(val_offsets ? n * 4 : 0);
+    void* ws = nullptr;
+    if ((rc = get_workspace(s, o_out + (out ? a.total : 0), &ws, kWsVlogEncIO))) return rc;
+    char* b = static_cast<char*>(ws);
+    if (kb) HIP_TRY(hipMemcpyAsync(b, keys + ko[0], kb, hipMemcpyHostToDevice, s));
+    if (offsets) HIP_TRY(hipMemcpyAsync(b + o_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (vb) HIP_TRY(hipMemcpyAsync(b + o_val, values + vo[0], vb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b + o_voff, value_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (created_ms) HIP_TRY(hipMemcpyAsync(b + o_cr, created_ms, n * 8, hipMemcpyHostToDevice, s));
+    if (tombstones) HIP_TRY(hipMemcpyAsync(b + o_tb, tombstones, n, hipMemcpyHostToDevice, s));
+    // both offset arrays hold absolute positions: the device copies start at keys + offsets[0] and
+    // values + value_off[0]
+    a.keys = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(b) - ko[0]);
+    a.values = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(b + o_val) - vo[0]);
+    a.offsets = offsets ? reinterpret_cast<const uint64_t*>(b + o_off) : nullptr;
+    a.value_off = reinterpret_cast<const uint64_t*>(b + o_voff);
+    a.created = created_ms ? reinterpret_cast<const int64_t*>(b + o_cr) : nullptr;
+    a.tomb = tombstones ? reinterpret_cast<const uint8_t*>(b + o_tb) : nullptr;
+    a.val_offsets = val_offsets ? reinterpret_cast<uint32_t*>(b + o_vo) : nullptr;
+    a.out = out ? reinterpret_cast<uint8_t*>(b + o_out) : nullptr;
+    if ((rc = vlog_enc_emit(a, s))) {
+        (void)hipStreamSynchronize(s);  // the uploads read the caller's buffers
+        return rc;
+    }
+    if (out && a.total) HIP_TRY(hipMemcpyAsync(out, a.out, a.total, hipMemcpyDeviceToHost, s));
+    if (val_offsets) HIP_TRY(hipMemcpyAsync(val_offsets, a.val_offsets, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return ok();
 }
 

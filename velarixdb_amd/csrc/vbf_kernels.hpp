@@ -32,7 +32,8 @@ enum Phase { kPhaseTileSort = 0, kPhaseTranspose = 1, kPhaseSegOr = 2, kPhaseAto
              kPhaseMergeLevels = 8, kPhaseFold = 9, kPhaseSelect = 10, kPhaseProbePack = 11,
              kPhaseProbeSeg = 12, kPhaseProbeOut = 13, kPhaseEncTile = 14, kPhaseEncScan = 15,
              kPhaseEncIndex = 16, kPhaseEncData = 17, kPhaseTableOpen = 18, kPhaseTableGet = 19,
-             kPhaseScanRank = 20, kPhaseScanEmit = 21, kNumPhases = 22 };
+             kPhaseScanRank = 20, kPhaseScanEmit = 21, kPhaseVlogSizes = 22, kPhaseVlogCopy = 23,
+             kPhaseVlogEncode = 24, kNumPhases = 25 };
 void phase_begin(int phase, hipStream_t s);
 void phase_end(int phase, hipStream_t s);
 
@@ -215,6 +216,48 @@ hipError_t table_scan_bounds(const TableScanArgs& a, hipStream_t s);
 hipError_t table_scan_rank(const TableScanArgs& a, hipStream_t s);
 hipError_t table_scan_emit(const TableScanArgs& a, hipStream_t s);
 hipError_t table_scan_keys(const TableScanArgs& a, hipStream_t s);
+// Value-log reads and appends (vbf_vlog.hip).  The copies divide their work by output bytes: one
+// workgroup per kVlogSlice bytes of the destination (a power of two between 1 KiB and 128 KiB).
+constexpr uint32_t kVlogSlice = 16384;
+enum : uint8_t { kVlogSkipped = 0, kVlogValue = 1, kVlogTombstone = 2, kVlogNone = 3, kVlogBad = 4,
+                 kVlogKeyMismatch = 5 };
+struct VlogGetArgs {
+    const uint8_t* bytes;         // the log's bytes [base, base + len)
+    uint64_t len, base;
+    const uint32_t* val_offsets;  // [n] file positions
+    const uint8_t* found;         // [n] or NULL: item j is fetched only when found[j] == 1
+    uint64_t n;
+    const uint8_t* keys;          // NULL: no key check; else the layout of every entry point
+    const uint64_t* offsets;
+    uint64_t stride;
+    uint8_t* status;              // [n] kVlog* (sizes pass)
+    uint64_t* vlen;               // [n + 1] value length, 0 unless status == kVlogValue; [n] = 0
+    uint64_t* src;                // [n] the value's position in `bytes`
+    const uint64_t* voff;         // [n + 1] exclusive scan of vlen; [n] = total
+    uint64_t total;
+    uint8_t* values;              // output of the copy pass
+};
+hipError_t vlog_sizes(const VlogGetArgs& a, hipStream_t s);
+hipError_t vlog_copy(const VlogGetArgs& a, hipStream_t s);
+enum : uint32_t { kVlogEncErrOrder = 1, kVlogEncErrLong = 2 };
+struct VlogEncArgs {
+    const uint8_t* keys;
+    const uint64_t* offsets;      // n + 1 absolute positions, or NULL for `stride`
+    uint64_t stride, n;
+    const uint8_t* values;
+    const uint64_t* value_off;    // n + 1 absolute positions in values
+    const int64_t* created;       // NULL: zeros
+    const uint8_t* tomb;          // NULL: zeros
+    uint64_t base;                // the file's size before the append
+    uint64_t k0, v0;              // offsets[0] (0 with a stride), value_off[0]
+    uint64_t k_end, v_end;        // offsets[n] (n * stride), value_off[n]: no byte at or past them is read
+    uint64_t total;               // bytes appended
+    uint32_t* err;                // check pass: [0] kVlogEncErr bits, [1] first bad entry
+    uint8_t* out;                 // outputs, each may be NULL
+    uint32_t* val_offsets;
+};
+hipError_t vlog_enc_check(const VlogEncArgs& a, hipStream_t s);
+hipError_t vlog_encode(const VlogEncArgs& a, hipStream_t s);
 // Batched probe across SSTs (vbf_multi.hip).
 struct MultiSst {
     const uint32_t* words;

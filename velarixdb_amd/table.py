@@ -18,6 +18,9 @@ in every table in one launch (vbf_table_get_host, velarixdb_amd/csrc/vbf_table.h
       the key side of DataStore::seek (src/range/range_iterator.rs:47-60) for a batch of (lo, hi)
       ranges: per range, in key order, every key inside the bounds that get_many would find, with
       get_many's answer for it (C ABI vbf_table_scan_host, velarixdb_amd/csrc/vbf_table_scan.hip).
+  get_values(keys, tables, vlog, filters=None, check_keys=False) -> (GetResult, Values)
+  scan_values(ranges, tables, vlog, ...)                         -> (ScanResult, Values)
+      the same two, followed by the value-log read of every live answer (velarixdb_amd/vlog.py).
 """
 import ctypes
 from dataclasses import dataclass
@@ -168,3 +171,23 @@ def scan_many(ranges, tables, keep_tombstones=False, end_exclusive=False):
     except VbfError as e:
         _raise("table_scan", e)
     return res
+
+
+def get_values(keys, tables, vlog, filters=None, check_keys=False):
+    """A batched get that ends in values: get_many, then the value-log read of every live winner
+    (DataStore::get_value_from_vlog, src/db/store.rs:628-641) -> (GetResult, vlog.Values).  Items
+    that were not found, or whose winner is a tombstone, are SKIPPED in the Values.  check_keys makes
+    every fetch check that the log's entry holds the searched key (the reference does not)."""
+    b = keys if isinstance(keys, HostBatch) else pack(keys)
+    res = get_many(b, tables, filters)
+    return res, vlog.get_many(res.val_offsets, found=res.found, keys=b if check_keys else None)
+
+
+def scan_values(ranges, tables, vlog, keep_tombstones=False, end_exclusive=False, check_keys=False):
+    """scan_many, then the value-log read of every listed live entry -> (ScanResult, vlog.Values);
+    a listed tombstone (keep_tombstones) is SKIPPED in the Values."""
+    from .keys import pack_offsets
+    res = scan_many(ranges, tables, keep_tombstones=keep_tombstones, end_exclusive=end_exclusive)
+    found = np.where(res.tombstones != 0, FOUND_TOMBSTONE, FOUND_LIVE).astype(np.uint8)
+    keys = pack_offsets(res.keys, res.key_off) if check_keys else None
+    return res, vlog.get_many(res.val_offsets, found=found, keys=keys)
