@@ -362,6 +362,37 @@ def test_capacity(vbf):
         same(get_dev(L.dev[1], vo), want)          # the stream and the workspaces are fine afterwards
 
 
+def test_get_host_values_workspace_refused(vbf):
+    """vbf_vlog_get_host refused the workspace for the values (VBF_WS_MAX_BYTES below their total): it
+    fails after queueing the downloads of status and value_off into the caller's arrays, so it returns
+    through the call scope's drain.  Four 64 KiB values under a 64 KiB cap: the I/O workspace (four
+    val_offsets: 256 bytes) and the sizing workspace (four 256-byte parts and the scan's scratch for
+    five items) fit, the 256 KiB of values do not; value_bytes, written after the sizing pass, shows
+    that only the values' workspace was refused."""
+    from velarixdb_amd._lib import VBF_ENOMEM, lib
+    rng = np.random.default_rng(0x3F05)
+    n, vlen = 4, 65536
+    log, offs = vr.encode([(b"k%d" % j, rng.bytes(vlen), T0 + j, 0) for j in range(n)], base=0)
+    vo = np.array(offs, np.uint32)
+    want = vr.get_many(log, vo)
+    with Logs(log) as L:
+        status, values = np.full(n, GUARD, np.uint8), np.full(n * vlen, GUARD, np.uint8)
+        voff = np.full(n + 1, 77, np.uint64)
+        vb = ctypes.c_uint64(77)
+        args = (L.host, vo.ctypes.data, None, n, None, None, 0, status.ctypes.data, values.ctypes.data, values.size,
+                voff.ctypes.data, ctypes.byref(vb))
+        os.environ["VBF_WS_MAX_BYTES"] = str(vlen)
+        try:
+            rc, err = lib.vbf_vlog_get_host(*args), lib.vbf_last_error()
+        finally:
+            os.environ.pop("VBF_WS_MAX_BYTES", None)
+        assert rc == VBF_ENOMEM and b"VBF_WS_MAX_BYTES" in err, (rc, err)
+        assert vb.value == n * vlen
+        rc = lib.vbf_vlog_get_host(*args)
+        assert rc == 0, lib.vbf_last_error()
+        same((status, values, voff, vb.value), want, "host")
+
+
 # ---- 5. encode ------------------------------------------------------------------------------
 
 def enc_inputs(entries, lead, vlead, stride=None):

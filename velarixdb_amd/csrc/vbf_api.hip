@@ -425,9 +425,9 @@ void par_memcpy(void* dst, const void* src, size_t n) {
 struct Staging {
     std::mutex mu;
     // The device's shared stream (filter_stream) and the workspaces cached on it belong to one host
-    // entry point at a time: held from before the call's first get_workspace on that stream until
-    // after its last hipStreamSynchronize (HostCall).  A lock of its own, not `mu`: `mu` guards the
-    // two staging streams and their buffers, which no holder of host_mu touches, so a long
+    // entry point at a time: HostCall takes it before the call's first get_workspace on that stream
+    // and releases it after draining the stream, on every return.  A lock of its own, not `mu`: `mu`
+    // guards the two staging streams and their buffers, which no holder of host_mu touches, so a long
     // vbf_build_host keeps overlapping the read path's gets and scans as before.
     // Lock order: filter lock(s) (Storage::mu, address order), then host_mu.  No holder waits for a
     // device worker's job (jobs_cv) or takes another device's host_mu.
@@ -555,12 +555,6 @@ Staging* staging_for(int device) {
     if (!g_staging[device]) g_staging[device].reset(new Staging());
     return g_staging[device].get();
 }
-
-// One host entry point's turn on `device`'s shared stream and its workspaces (Staging::host_mu).
-struct HostCall {
-    std::unique_lock<std::mutex> lk;
-    explicit HostCall(int device) : lk(staging_for(device)->host_mu) {}
-};
 
 // Streams host keys through the staging buffers, calling launch(batch_on_device, first_key,
 // buffer_index, stream) per chunk.  After the loop both streams are synchronized.
@@ -880,6 +874,96 @@ int filter_stream(int device, hipStream_t* out) {
     return VBF_OK;
 }
 
+inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
+
+// One host entry point's scope on `device` (HOST_CALL): the device's shared stream `s` and the
+// call's turn on that stream and its workspaces (Staging::host_mu).  Every return that does not
+// follow finish (or settled) drains the stream in the destructor, before the lock is released and,
+// HOST_CALL's device guard being older, before the previous device is restored: no failing return
+// leaves work in flight that reads or writes the caller's buffers, the call's locals or a workspace
+// the next holder may grow.  Declared after the locals its copies use; filter locks and their drain
+// are taken before it (host_mu's lock order).
+struct HostCall {
+    std::unique_lock<std::mutex> lk;
+    hipStream_t s = nullptr;
+    bool drained = false;
+    std::vector<std::vector<uint64_t>> rebased;  // up_rebased's sources, kept until the drain
+
+    ~HostCall() {
+        if (s && !drained) (void)hipStreamSynchronize(s);
+    }
+    int begin(int device) {  // on `device` (DEVICE_SCOPE)
+        if (int rc = filter_stream(device, &s)) return rc;
+        lk = std::unique_lock<std::mutex>(staging_for(device)->host_mu);
+        return VBF_OK;
+    }
+    // Host <-> device copies of `count` elements; nothing when count == 0 or the host side is NULL.
+    int copy(void* dst, const void* src, uint64_t bytes, hipMemcpyKind kind) {
+        if (bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, s));
+        return VBF_OK;
+    }
+    template <class T>
+    int up(T* dst, const T* src, uint64_t count) {
+        return src ? copy(dst, src, count * sizeof(T), hipMemcpyHostToDevice) : VBF_OK;
+    }
+    template <class T>
+    int down(T* dst, const T* src, uint64_t count) {
+        return dst ? copy(dst, src, count * sizeof(T), hipMemcpyDeviceToHost) : VBF_OK;
+    }
+    // offsets[i] - offsets[0]: positions in a device copy that starts at the first offset.
+    int up_rebased(uint64_t* dst, const uint64_t* offsets, uint64_t count) {
+        if (!count || !offsets) return VBF_OK;
+        rebased.emplace_back(offsets, offsets + count);
+        for (auto& x : rebased.back()) x -= offsets[0];
+        return up(dst, rebased.back().data(), count);
+    }
+    int sync() {  // the mid-call drains
+        HIP_TRY(hipStreamSynchronize(s));
+        return VBF_OK;
+    }
+    int finish() {  // the success path's last drain
+        int rc = sync();
+        drained = !rc;
+        return rc ? rc : ok();
+    }
+    // For a success path that enqueued nothing, or ends in a core call that returns synchronised.
+    void settled() { drained = true; }
+};
+
+// DEVICE_SCOPE, then the host call's scope `name`; returns either's error.
+#define HOST_CALL(name, dev) \
+    DEVICE_SCOPE(dev);       \
+    HostCall name;           \
+    if (int hrc_ = name.begin(dev)) return hrc_
+
+// A device image: parts laid end to end in the order added, each on a 256-byte boundary.
+template <class T>
+struct Part {
+    uint64_t off;
+    bool present;
+};
+struct DevImage {
+    uint64_t bytes = 0;  // the last part's end
+    void* base = nullptr;
+    template <class T>
+    Part<T> add(uint64_t count, bool present = true) {
+        const Part<T> p{align256(bytes), present};
+        bytes = p.off + (present ? count * sizeof(T) : 0);
+        return p;
+    }
+    int alloc(HostCall& call, int slot) { return get_workspace(call.s, bytes, &base, slot); }
+    template <class T>
+    T* ptr(Part<T> p) const {
+        return p.present ? reinterpret_cast<T*>(static_cast<char*>(base) + p.off) : nullptr;
+    }
+};
+
+// For offsets that are absolute positions in the caller's arena: the pointer they index, given the
+// device copy `dev` of the arena's bytes from `first` on.
+const uint8_t* arena_base(const uint8_t* dev, uint64_t first) {
+    return reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(dev) - first);
+}
+
 // Caller holds s.mu (drained), on s.device: the mirror holds the current bits (one D2H when
 // it is stale).
 int mirror_fill(Storage& s) {
@@ -955,8 +1039,6 @@ namespace {
 // SST data.db decode (vbf_sst.hip): count pass + scan, one 16-byte readback (entry total and
 // error word) so the caller can size or validate, then the emit pass queued on the stream.
 // ---------------------------------------------------------------------------------------
-inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
-
 int sst_count_pass(const uint8_t* data, uint64_t len, const uint32_t* blocks, uint64_t nblocks,
                    hipStream_t s, vbf::SstArgs* a, uint64_t* n_out, uint32_t* uniform_len = nullptr) {
     *a = vbf::SstArgs{};
@@ -1023,6 +1105,20 @@ int sst_count_pass(const uint8_t* data, uint64_t len, const uint32_t* blocks, ui
     if (len < 17 * total) return fail(VBF_EINVAL, "inconsistent entry count %llu", (unsigned long long)total);
     *n_out = total;
     if (uniform_len && total && ev[2] == ev[3] && a->ablate == 0) *uniform_len = ev[2];
+    return VBF_OK;
+}
+
+// vbf_sst_decode_*: the caller's outputs (NULL = not asked for) hold n entries and kb key bytes.
+int sst_decode_caps(bool entry_arrays, bool offsets, bool keys, uint64_t entries_cap, uint64_t keys_cap, uint64_t n,
+                    uint64_t kb) {
+    if (entry_arrays && entries_cap < n)
+        return fail(VBF_EINVAL, "entry arrays hold %llu < %llu entries", (unsigned long long)entries_cap,
+                    (unsigned long long)n);
+    if (offsets && entries_cap < n + 1)
+        return fail(VBF_EINVAL, "offsets holds %llu < %llu entries", (unsigned long long)entries_cap,
+                    (unsigned long long)(n + 1));
+    if (keys && keys_cap < kb)
+        return fail(VBF_EINVAL, "keys holds %llu < %llu bytes", (unsigned long long)keys_cap, (unsigned long long)kb);
     return VBF_OK;
 }
 
@@ -2334,15 +2430,9 @@ int vbf_sst_decode_dev(const uint8_t* data, uint64_t len, const uint32_t* blocks
     vbf::SstArgs a;
     int rc = sst_count_pass(data, len, blocks, nblocks, s, &a, n_out);
     if (rc) return rc;
-    const uint64_t n = *n_out, kb = len - 17 * n;
-    if ((val_offsets || created_ms || tombstones) && entries_cap < n)
-        return fail(VBF_EINVAL, "entry arrays hold %llu < %llu entries", (unsigned long long)entries_cap,
-                    (unsigned long long)n);
-    if (offsets && entries_cap < n + 1)
-        return fail(VBF_EINVAL, "offsets holds %llu < %llu entries", (unsigned long long)entries_cap,
-                    (unsigned long long)(n + 1));
-    if (keys && keys_cap < kb)
-        return fail(VBF_EINVAL, "keys holds %llu < %llu bytes", (unsigned long long)keys_cap, (unsigned long long)kb);
+    if ((rc = sst_decode_caps(val_offsets || created_ms || tombstones, offsets, keys, entries_cap, keys_cap, *n_out,
+                              len - 17 * *n_out)))
+        return rc;
     if ((rc = sst_emit_pass(a, keys, offsets, val_offsets, created_ms, tombstones, s))) return rc;
     return ok();
 }
@@ -2354,47 +2444,32 @@ int vbf_sst_decode_host(const uint8_t* data, uint64_t len, const uint8_t* index,
     std::vector<uint32_t> blk;
     int rc = parse_index(index, index_len, &blk);
     if (rc) return rc;
-    DEVICE_SCOPE(device);
-    hipStream_t s;
-    if ((rc = filter_stream(device, &s))) return rc;
-    HostCall turn(device);
-    // device image: data | blocks | then the outputs (count pass first, to size them)
-    const uint64_t o_blk = align256(len), o_end = o_blk + align256(blk.size() * 4);
-    void* in = nullptr;
-    if ((rc = get_workspace(s, o_end, &in, kWsSstInput))) return rc;
-    uint8_t* d_data = static_cast<uint8_t*>(in);
-    uint32_t* d_blk = reinterpret_cast<uint32_t*>(d_data + o_blk);
-    if (len) HIP_TRY(hipMemcpyAsync(d_data, data, len, hipMemcpyHostToDevice, s));
-    if (blk.size()) HIP_TRY(hipMemcpyAsync(d_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, s));
+    HOST_CALL(call, device);
+    // device image: data | blocks, then the outputs (count pass first, to size them)
+    DevImage in;
+    const auto p_data = in.add<uint8_t>(len);
+    const auto p_blk = in.add<uint32_t>(blk.size());
+    if ((rc = in.alloc(call, kWsSstInput))) return rc;
+    if ((rc = call.up(in.ptr(p_data), data, len)) || (rc = call.up(in.ptr(p_blk), blk.data(), blk.size()))) return rc;
     vbf::SstArgs a;
-    if ((rc = sst_count_pass(d_data, len, d_blk, blk.size(), s, &a, n_out))) return rc;
+    if ((rc = sst_count_pass(in.ptr(p_data), len, in.ptr(p_blk), blk.size(), call.s, &a, n_out))) return rc;
     const uint64_t n = *n_out, kb = len - 17 * n;
-    if ((val_offsets || created_ms || tombstones) && entries_cap < n)
-        return fail(VBF_EINVAL, "entry arrays hold %llu < %llu entries", (unsigned long long)entries_cap,
-                    (unsigned long long)n);
-    if (offsets && entries_cap < n + 1)
-        return fail(VBF_EINVAL, "offsets holds %llu < %llu entries", (unsigned long long)entries_cap,
-                    (unsigned long long)(n + 1));
-    if (keys && keys_cap < kb)
-        return fail(VBF_EINVAL, "keys holds %llu < %llu bytes", (unsigned long long)keys_cap, (unsigned long long)kb);
-    const uint64_t o_keys = 0, o_off = align256(kb), o_val = o_off + align256((n + 1) * 8);
-    const uint64_t o_cr = o_val + align256(n * 4), o_tb = o_cr + align256(n * 8), total = o_tb + align256(n);
-    void* out = nullptr;
-    if ((rc = get_workspace(s, total, &out, kWsSstKeys))) return rc;
-    char* ob = static_cast<char*>(out);
-    uint8_t* d_keys = keys ? reinterpret_cast<uint8_t*>(ob + o_keys) : nullptr;
-    uint64_t* d_off = offsets ? reinterpret_cast<uint64_t*>(ob + o_off) : nullptr;
-    uint32_t* d_val = val_offsets ? reinterpret_cast<uint32_t*>(ob + o_val) : nullptr;
-    uint64_t* d_cr = created_ms ? reinterpret_cast<uint64_t*>(ob + o_cr) : nullptr;
-    uint8_t* d_tb = tombstones ? reinterpret_cast<uint8_t*>(ob + o_tb) : nullptr;
-    if ((rc = sst_emit_pass(a, d_keys, d_off, d_val, d_cr, d_tb, s))) return rc;
-    if (keys && kb) HIP_TRY(hipMemcpyAsync(keys, d_keys, kb, hipMemcpyDeviceToHost, s));
-    if (offsets) HIP_TRY(hipMemcpyAsync(offsets, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (val_offsets && n) HIP_TRY(hipMemcpyAsync(val_offsets, d_val, n * 4, hipMemcpyDeviceToHost, s));
-    if (created_ms && n) HIP_TRY(hipMemcpyAsync(created_ms, d_cr, n * 8, hipMemcpyDeviceToHost, s));
-    if (tombstones && n) HIP_TRY(hipMemcpyAsync(tombstones, d_tb, n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ok();
+    if ((rc = sst_decode_caps(val_offsets || created_ms || tombstones, offsets, keys, entries_cap, keys_cap, n, kb)))
+        return rc;
+    DevImage out;  // keys | offsets | val | created | tombstones
+    const auto p_keys = out.add<uint8_t>(kb, keys);
+    const auto p_off = out.add<uint64_t>(n + 1, offsets);
+    const auto p_val = out.add<uint32_t>(n, val_offsets);
+    const auto p_cr = out.add<uint64_t>(n, created_ms);
+    const auto p_tb = out.add<uint8_t>(n, tombstones);
+    if ((rc = out.alloc(call, kWsSstKeys))) return rc;
+    if ((rc = sst_emit_pass(a, out.ptr(p_keys), out.ptr(p_off), out.ptr(p_val), out.ptr(p_cr), out.ptr(p_tb), call.s)))
+        return rc;
+    if ((rc = call.down(keys, out.ptr(p_keys), kb)) || (rc = call.down(offsets, out.ptr(p_off), n + 1)) ||
+        (rc = call.down(val_offsets, out.ptr(p_val), n)) || (rc = call.down(created_ms, out.ptr(p_cr), n)) ||
+        (rc = call.down(tombstones, out.ptr(p_tb), n)))
+        return rc;
+    return call.finish();
 }
 
 // ---- SST data.db / index.db encode ----
@@ -2424,46 +2499,35 @@ int vbf_sst_encode_host(const uint8_t* keys, const uint64_t* offsets, uint64_t s
     if (!keys && kb) return fail(VBF_EINVAL, "keys is NULL");
     if (n >= (1ull << 32) / 17 || kb >= (1ull << 32))
         return fail(VBF_EINVAL, "data.db reaches 2^32 bytes: index.db's u32 block offsets cannot address it");
-    DEVICE_SCOPE(device);
-    hipStream_t s;
-    int rc = filter_stream(device, &s);
-    if (rc) return rc;
-    HostCall turn(device);
+    HOST_CALL(call, device);
+    int rc;
     // device image: keys | offsets | val | created | tombstones | data | index | blocks, the outputs
     // at the sizes that always suffice (or the caller's capacity when that is smaller)
     const uint64_t dcap = data ? std::min(data_cap, kb + 17 * n) : 0, icap = index ? std::min(index_cap, kb + 8 * n) : 0;
     const uint64_t bcap = blocks ? std::min(blocks_cap, n) : 0;
-    const uint64_t o_off = align256(kb), o_val = o_off + align256(offsets ? (n + 1) * 8 : 0);
-    const uint64_t o_cr = o_val + align256(val_offsets ? n * 4 : 0), o_tb = o_cr + align256(created_ms ? n * 8 : 0);
-    const uint64_t o_data = o_tb + align256(tombstones ? n : 0), o_idx = o_data + align256(dcap);
-    const uint64_t o_blk = o_idx + align256(icap), bytes = o_blk + align256(bcap * 4);
-    void* ws = nullptr;
-    if ((rc = get_workspace(s, bytes, &ws, kWsSstEncIO))) return rc;
-    char* b = static_cast<char*>(ws);
-    if (kb) HIP_TRY(hipMemcpyAsync(b, keys + k0, kb, hipMemcpyHostToDevice, s));
-    if (offsets) HIP_TRY(hipMemcpyAsync(b + o_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (val_offsets) HIP_TRY(hipMemcpyAsync(b + o_val, val_offsets, n * 4, hipMemcpyHostToDevice, s));
-    if (created_ms) HIP_TRY(hipMemcpyAsync(b + o_cr, created_ms, n * 8, hipMemcpyHostToDevice, s));
-    if (tombstones) HIP_TRY(hipMemcpyAsync(b + o_tb, tombstones, n, hipMemcpyHostToDevice, s));
-    // offsets are absolute positions in `keys`: the device copy starts at keys + offsets[0]
-    const uint8_t* d_keys = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(b) - k0);
-    uint8_t* d_data = data ? reinterpret_cast<uint8_t*>(b + o_data) : nullptr;
-    uint8_t* d_idx = index ? reinterpret_cast<uint8_t*>(b + o_idx) : nullptr;
-    uint32_t* d_blk = blocks ? reinterpret_cast<uint32_t*>(b + o_blk) : nullptr;
-    rc = sst_encode(d_keys, offsets ? reinterpret_cast<const uint64_t*>(b + o_off) : nullptr, stride, n,
-                    val_offsets ? reinterpret_cast<const uint32_t*>(b + o_val) : nullptr,
-                    created_ms ? reinterpret_cast<const int64_t*>(b + o_cr) : nullptr,
-                    tombstones ? reinterpret_cast<const uint8_t*>(b + o_tb) : nullptr, d_data, dcap, data_len, d_idx, icap,
-                    index_len, d_blk, bcap, nblocks, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);  // the uploads read the caller's buffers
+    DevImage img;
+    const auto p_keys = img.add<uint8_t>(kb);
+    const auto p_off = img.add<uint64_t>(n + 1, offsets);
+    const auto p_val = img.add<uint32_t>(n, val_offsets);
+    const auto p_cr = img.add<int64_t>(n, created_ms);
+    const auto p_tb = img.add<uint8_t>(n, tombstones);
+    const auto p_data = img.add<uint8_t>(dcap, data);
+    const auto p_idx = img.add<uint8_t>(icap, index);
+    const auto p_blk = img.add<uint32_t>(bcap, blocks);
+    if ((rc = img.alloc(call, kWsSstEncIO))) return rc;
+    if ((rc = call.up(img.ptr(p_keys), kb ? keys + k0 : nullptr, kb)) || (rc = call.up(img.ptr(p_off), offsets, n + 1)) ||
+        (rc = call.up(img.ptr(p_val), val_offsets, n)) || (rc = call.up(img.ptr(p_cr), created_ms, n)) ||
+        (rc = call.up(img.ptr(p_tb), tombstones, n)))
         return rc;
-    }
-    if (data && *data_len) HIP_TRY(hipMemcpyAsync(data, d_data, *data_len, hipMemcpyDeviceToHost, s));
-    if (index && *index_len) HIP_TRY(hipMemcpyAsync(index, d_idx, *index_len, hipMemcpyDeviceToHost, s));
-    if (blocks && *nblocks) HIP_TRY(hipMemcpyAsync(blocks, d_blk, *nblocks * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ok();
+    // offsets are absolute positions in `keys`: the device copy starts at keys + offsets[0]
+    if ((rc = sst_encode(arena_base(img.ptr(p_keys), k0), img.ptr(p_off), stride, n, img.ptr(p_val), img.ptr(p_cr),
+                         img.ptr(p_tb), img.ptr(p_data), dcap, data_len, img.ptr(p_idx), icap, index_len,
+                         img.ptr(p_blk), bcap, nblocks, call.s)))
+        return rc;
+    if ((rc = call.down(data, img.ptr(p_data), *data_len)) || (rc = call.down(index, img.ptr(p_idx), *index_len)) ||
+        (rc = call.down(blocks, img.ptr(p_blk), *nblocks)))
+        return rc;
+    return call.finish();
 }
 
 // range.rs:117-128 (load_entries_from_file + build_filter_from_entries) on the device: decode
@@ -2523,20 +2587,14 @@ int vbf_filter_rebuild_from_sst_host(vbf_filter* f, const uint8_t* data, uint64_
     std::unique_lock<std::mutex> lk(s.mu);
     if ((rc = storage_drain(s, lk))) return rc;
     if (s.host()) return host_resident("vbf_filter_rebuild_from_sst_host");
-    DEVICE_SCOPE(s.device);
-    hipStream_t st;
-    if ((rc = filter_stream(s.device, &st))) return rc;
-    HostCall turn(s.device);  // after the filter's lock and its drain
-    const uint64_t o_blk = align256(len), o_end = o_blk + align256(blk.size() * 4);
-    void* in = nullptr;
-    if ((rc = get_workspace(st, o_end, &in, kWsSstInput))) return rc;
-    uint8_t* d_data = static_cast<uint8_t*>(in);
-    uint32_t* d_blk = reinterpret_cast<uint32_t*>(d_data + o_blk);
-    if (len) HIP_TRY(hipMemcpyAsync(d_data, data, len, hipMemcpyHostToDevice, st));
-    if (blk.size()) HIP_TRY(hipMemcpyAsync(d_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, st));
-    if ((rc = rebuild_locked(f, s, d_data, len, d_blk, blk.size(), n_out, st))) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    return ok();
+    HOST_CALL(call, s.device);  // after the filter's lock and its drain
+    DevImage in;  // data | blocks
+    const auto p_data = in.add<uint8_t>(len);
+    const auto p_blk = in.add<uint32_t>(blk.size());
+    if ((rc = in.alloc(call, kWsSstInput))) return rc;
+    if ((rc = call.up(in.ptr(p_data), data, len)) || (rc = call.up(in.ptr(p_blk), blk.data(), blk.size()))) return rc;
+    if ((rc = rebuild_locked(f, s, in.ptr(p_data), len, in.ptr(p_blk), blk.size(), n_out, call.s))) return rc;
+    return call.finish();
 }
 
 }  // extern "C"
@@ -2783,32 +2841,22 @@ namespace {
 int multi_probe_host_device(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
                             int len_prefix, uint32_t nsst, const vbf_filter* const* filters, const uint8_t* bounds,
                             const uint64_t* bounds_off, uint8_t* out, int device) {
-    DEVICE_SCOPE(device);
-    hipStream_t s;
-    int rc = filter_stream(device, &s);
-    if (rc) return rc;
-    HostCall turn(device);  // this device's part only: the multi-device path takes each in turn
-    const uint64_t kbytes = offsets ? offsets[n] - offsets[0] : n * stride;
-    const uint64_t o_off = align256(kbytes), o_out = o_off + align256(offsets ? (n + 1) * 8 : 0);
-    void* ws = nullptr;
-    if ((rc = get_workspace(s, o_out + n * nsst, &ws, kWsMultiKeys))) return rc;
-    uint8_t* d_keys = static_cast<uint8_t*>(ws);
-    uint64_t* d_off = offsets ? reinterpret_cast<uint64_t*>(d_keys + o_off) : nullptr;
-    uint8_t* d_out = d_keys + o_out;
-    if (kbytes) HIP_TRY(hipMemcpyAsync(d_keys, keys + (offsets ? offsets[0] : 0), kbytes, hipMemcpyHostToDevice, s));
-    if (offsets) {
-        // rebase to absolute positions in the device copy
-        std::vector<uint64_t> o(offsets, offsets + n + 1);
-        const uint64_t b0 = o[0];
-        for (auto& x : o) x -= b0;
-        HIP_TRY(hipMemcpyAsync(d_off, o.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    if ((rc = multi_probe(d_keys, d_off, stride, n, len_prefix, nsst, filters, bounds, bounds_off, d_out, s)))
+    HOST_CALL(call, device);  // this device's part only: the multi-device path takes each in turn
+    int rc;
+    const uint64_t k0 = offsets ? offsets[0] : 0, kbytes = offsets ? offsets[n] - k0 : n * stride;
+    DevImage img;  // keys | offsets | answers
+    const auto p_keys = img.add<uint8_t>(kbytes);
+    const auto p_off = img.add<uint64_t>(n + 1, offsets);
+    const auto p_out = img.add<uint8_t>(n * nsst);
+    if ((rc = img.alloc(call, kWsMultiKeys))) return rc;
+    if ((rc = call.up(img.ptr(p_keys), kbytes ? keys + k0 : nullptr, kbytes))) return rc;
+    // absolute positions in the device copy
+    if (offsets && ((rc = call.up_rebased(img.ptr(p_off), offsets, n + 1)) || (rc = call.sync()))) return rc;
+    if ((rc = multi_probe(img.ptr(p_keys), img.ptr(p_off), stride, n, len_prefix, nsst, filters, bounds, bounds_off,
+                          img.ptr(p_out), call.s)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out, n * nsst, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VBF_OK;
+    if ((rc = call.down(out, img.ptr(p_out), n * nsst))) return rc;
+    return call.finish();
 }
 
 // vbf_multi_probe_host over filters split into groups (group[i] of filter i; the multi-device
@@ -3093,6 +3141,46 @@ int gather_entries(const uint8_t* keys, const uint64_t* offsets, const int64_t* 
     HIP_TRY(vbf::gather(g, s));
     return VBF_OK;
 }
+
+// The device image of vbf_compact_merge_host and _write_host: the arena (keys | offsets | created |
+// tombstones | val_offsets, write only | map keys | map offsets | map times), then the merge's
+// outputs (ids | updated ids | updated times).
+struct CompactImage : DevImage {
+    Part<uint8_t> keys, tb, mk;
+    Part<uint64_t> off, mo;
+    Part<int64_t> cr, mt, ut;
+    Part<uint32_t> val, ids, ui;
+};
+
+// Lays the image out, allocates it and uploads the arena (one stream synchronisation: the sources
+// are pageable).  with_val without the caller's val_offsets: that part is zero-filled.
+int compact_stage(HostCall& c, CompactImage& m, const uint8_t* keys, const uint64_t* offsets, const int64_t* created,
+                  const uint8_t* tomb, uint64_t total, bool with_val, const uint32_t* val_offsets,
+                  const uint8_t* map_keys, const uint64_t* map_off, const int64_t* map_time, uint64_t map_n,
+                  bool want_upd) {
+    const uint64_t kb = offsets[total], mkb = map_n ? map_off[map_n] : 0;
+    m.keys = m.add<uint8_t>(kb);
+    m.off = m.add<uint64_t>(total + 1);
+    m.cr = m.add<int64_t>(total);
+    m.tb = m.add<uint8_t>(total);
+    m.val = m.add<uint32_t>(total, with_val);
+    m.mk = m.add<uint8_t>(mkb, map_n);
+    m.mo = m.add<uint64_t>(map_n + 1, map_n);
+    m.mt = m.add<int64_t>(map_n, map_n);
+    m.ids = m.add<uint32_t>(total);
+    m.ui = m.add<uint32_t>(total, want_upd);
+    m.ut = m.add<int64_t>(total, want_upd);
+    int rc = m.alloc(c, kWsCompactIn);
+    if (rc || (rc = c.up(m.ptr(m.keys), keys, kb)) || (rc = c.up(m.ptr(m.off), offsets, total + 1)) ||
+        (rc = c.up(m.ptr(m.cr), created, total)) || (rc = c.up(m.ptr(m.tb), tomb, total)) ||
+        (rc = c.up(m.ptr(m.val), val_offsets, total)))
+        return rc;
+    if (with_val && !val_offsets) HIP_TRY(hipMemsetAsync(m.ptr(m.val), 0, total * 4, c.s));
+    if (map_n && ((rc = c.up(m.ptr(m.mk), map_keys, mkb)) || (rc = c.up(m.ptr(m.mo), map_off, map_n + 1)) ||
+                  (rc = c.up(m.ptr(m.mt), map_time, map_n))))
+        return rc;
+    return c.sync();
+}
 }  // namespace
 
 extern "C" {
@@ -3132,47 +3220,21 @@ int vbf_compact_merge_host(const uint8_t* keys, const uint64_t* offsets, const i
                               out_ids, &total);
     if (rc) return rc;
     if (total == 0) return ok();  // no entries: nothing to merge, no device needed
-    DEVICE_SCOPE(device);
-    hipStream_t s;
-    if ((rc = filter_stream(device, &s))) return rc;
-    HostCall turn(device);
-    const uint64_t kb = total ? offsets[total] : 0, mkb = map_n ? map_off[map_n] : 0;
-    const uint64_t o_off = align256(kb), o_cr = o_off + align256((total + 1) * 8), o_tb = o_cr + align256(total * 8);
-    const uint64_t o_mk = o_tb + align256(total), o_mo = o_mk + align256(mkb), o_mt = o_mo + align256((map_n + 1) * 8);
-    const uint64_t o_ids = o_mt + align256(map_n * 8), o_ui = o_ids + align256(total * 4);
-    const uint64_t o_ut = o_ui + align256(total * 4), bytes = o_ut + align256(total * 8);
-    void* ws = nullptr;
-    if ((rc = get_workspace(s, bytes, &ws, kWsCompactIn))) return rc;
-    char* b = static_cast<char*>(ws);
-    if (kb) HIP_TRY(hipMemcpyAsync(b, keys, kb, hipMemcpyHostToDevice, s));
-    if (total) {
-        HIP_TRY(hipMemcpyAsync(b + o_off, offsets, (total + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b + o_cr, created_ms, total * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b + o_tb, tombstones, total, hipMemcpyHostToDevice, s));
-    }
-    if (map_n) {
-        if (mkb) HIP_TRY(hipMemcpyAsync(b + o_mk, map_keys, mkb, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b + o_mo, map_off, (map_n + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b + o_mt, map_time, map_n * 8, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
+    HOST_CALL(call, device);
     const bool want_upd = upd_ids && upd_time;
+    CompactImage m;
+    if ((rc = compact_stage(call, m, keys, offsets, created_ms, tombstones, total, false, nullptr, map_keys, map_off,
+                            map_time, map_n, want_upd)))
+        return rc;
     uint64_t nu = 0;
-    rc = compact_merge(reinterpret_cast<const uint8_t*>(b), reinterpret_cast<const uint64_t*>(b + o_off),
-                       reinterpret_cast<const int64_t*>(b + o_cr), reinterpret_cast<const uint8_t*>(b + o_tb), run_off,
-                       nruns, map_n ? reinterpret_cast<const uint8_t*>(b + o_mk) : nullptr,
-                       map_n ? reinterpret_cast<const uint64_t*>(b + o_mo) : nullptr,
-                       map_n ? reinterpret_cast<const int64_t*>(b + o_mt) : nullptr, map_n, use_ttl, entry_ttl_ms,
-                       tombstone_ttl_ms, now_ms, reinterpret_cast<uint32_t*>(b + o_ids), n_out,
-                       want_upd ? reinterpret_cast<uint32_t*>(b + o_ui) : nullptr,
-                       want_upd ? reinterpret_cast<int64_t*>(b + o_ut) : nullptr, &nu, s);
-    if (rc) return rc;
-    if (*n_out) HIP_TRY(hipMemcpyAsync(out_ids, b + o_ids, *n_out * 4, hipMemcpyDeviceToHost, s));
-    if (want_upd && nu) {
-        HIP_TRY(hipMemcpyAsync(upd_ids, b + o_ui, nu * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(upd_time, b + o_ut, nu * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = compact_merge(m.ptr(m.keys), m.ptr(m.off), m.ptr(m.cr), m.ptr(m.tb), run_off, nruns, m.ptr(m.mk),
+                            m.ptr(m.mo), m.ptr(m.mt), map_n, use_ttl, entry_ttl_ms, tombstone_ttl_ms, now_ms,
+                            m.ptr(m.ids), n_out, m.ptr(m.ui), m.ptr(m.ut), &nu, call.s)))
+        return rc;
+    if ((rc = call.down(out_ids, m.ptr(m.ids), *n_out)) ||
+        (want_upd && ((rc = call.down(upd_ids, m.ptr(m.ui), nu)) || (rc = call.down(upd_time, m.ptr(m.ut), nu)))) ||
+        (rc = call.finish()))
+        return rc;
     if (n_upd) *n_upd = nu;
     return ok();
 }
@@ -3198,77 +3260,47 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
     if (total == 0) return fail(VBF_EINVAL, "empty merge: BloomFilter::new asserts no_of_elements > 0 (bf.rs:67)");
     uint32_t m_probe, k_probe;  // bf.rs:63-66: the rate is checked before any work
     if ((rc = vbf_size(false_positive, total, &m_probe, &k_probe))) return rc;
-    DEVICE_SCOPE(device);
-    hipStream_t s;
-    if ((rc = filter_stream(device, &s))) return rc;
     // The one place a filter lock is taken under the device's: the merged table's filter is created
     // below and no other thread can reach it before this call returns it.
-    HostCall turn(device);
+    HOST_CALL(call, device);
     const bool want_upd = upd_ids && upd_time;
-    const uint64_t kb = offsets[total], mkb = map_n ? map_off[map_n] : 0;
-    const uint64_t o_off = align256(kb), o_cr = o_off + align256((total + 1) * 8), o_tb = o_cr + align256(total * 8);
-    const uint64_t o_val = o_tb + align256(total), o_mk = o_val + align256(total * 4), o_mo = o_mk + align256(mkb);
-    const uint64_t o_mt = o_mo + align256((map_n + 1) * 8), o_ids = o_mt + align256(map_n * 8);
-    const uint64_t o_ui = o_ids + align256(total * 4), o_ut = o_ui + align256(total * 4);
-    const uint64_t bytes = o_ut + align256(total * 8);
-    void* ws = nullptr;
-    if ((rc = get_workspace(s, bytes, &ws, kWsCompactIn))) return rc;
-    char* b = static_cast<char*>(ws);
-    if (kb) HIP_TRY(hipMemcpyAsync(b, keys, kb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b + o_off, offsets, (total + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b + o_cr, created_ms, total * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b + o_tb, tombstones, total, hipMemcpyHostToDevice, s));
-    if (val_offsets) HIP_TRY(hipMemcpyAsync(b + o_val, val_offsets, total * 4, hipMemcpyHostToDevice, s));
-    else HIP_TRY(hipMemsetAsync(b + o_val, 0, total * 4, s));
-    if (map_n) {
-        if (mkb) HIP_TRY(hipMemcpyAsync(b + o_mk, map_keys, mkb, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b + o_mo, map_off, (map_n + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b + o_mt, map_time, map_n * 8, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint8_t* a_keys = reinterpret_cast<const uint8_t*>(b);
-    const uint64_t* a_off = reinterpret_cast<const uint64_t*>(b + o_off);
-    const int64_t* a_cr = reinterpret_cast<const int64_t*>(b + o_cr);
-    const uint8_t* a_tb = reinterpret_cast<const uint8_t*>(b + o_tb);
-    const uint32_t* a_val = reinterpret_cast<const uint32_t*>(b + o_val);
-    const uint32_t* d_ids = reinterpret_cast<const uint32_t*>(b + o_ids);
+    CompactImage m;
+    if ((rc = compact_stage(call, m, keys, offsets, created_ms, tombstones, total, true, val_offsets, map_keys, map_off,
+                            map_time, map_n, want_upd)))
+        return rc;
     uint64_t n = 0, nu = 0;
-    rc = compact_merge(a_keys, a_off, a_cr, a_tb, run_off, nruns, map_n ? reinterpret_cast<const uint8_t*>(b + o_mk) : nullptr,
-                       map_n ? reinterpret_cast<const uint64_t*>(b + o_mo) : nullptr,
-                       map_n ? reinterpret_cast<const int64_t*>(b + o_mt) : nullptr, map_n, use_ttl, entry_ttl_ms,
-                       tombstone_ttl_ms, now_ms, reinterpret_cast<uint32_t*>(b + o_ids), &n,
-                       want_upd ? reinterpret_cast<uint32_t*>(b + o_ui) : nullptr,
-                       want_upd ? reinterpret_cast<int64_t*>(b + o_ut) : nullptr, &nu, s);
-    if (rc) return rc;
+    if ((rc = compact_merge(m.ptr(m.keys), m.ptr(m.off), m.ptr(m.cr), m.ptr(m.tb), run_off, nruns, m.ptr(m.mk),
+                            m.ptr(m.mo), m.ptr(m.mt), map_n, use_ttl, entry_ttl_ms, tombstone_ttl_ms, now_ms,
+                            m.ptr(m.ids), &n, m.ptr(m.ui), m.ptr(m.ut), &nu, call.s)))
+        return rc;
     // the map updates happen during the fold, before the merged table is looked at (sized.rs:286-320)
     if (want_upd && nu) {
-        HIP_TRY(hipMemcpyAsync(upd_ids, b + o_ui, nu * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(upd_time, b + o_ut, nu * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        if ((rc = call.down(upd_ids, m.ptr(m.ui), nu)) || (rc = call.down(upd_time, m.ptr(m.ut), nu)) ||
+            (rc = call.sync()))
+            return rc;
     }
     if (n_upd) *n_upd = nu;
     if (n == 0) return fail(VBF_EINVAL, "empty merge: BloomFilter::new asserts no_of_elements > 0 (bf.rs:67)");
     // merged table in the build's key layout, then its files; capacities that always suffice
-    const uint64_t q_off = align256(kb), q_cr = q_off + align256((n + 1) * 8), q_tb = q_cr + align256(n * 8);
-    const uint64_t q_val = q_tb + align256(n), q_data = q_val + align256(n * 4), q_idx = q_data + align256(kb + 17 * n);
-    const uint64_t q_end = q_idx + align256(kb + 8 * n);
-    void* ows = nullptr;
-    if ((rc = get_workspace(s, q_end, &ows, kWsCompactOut))) return rc;
-    char* q = static_cast<char*>(ows);
-    uint8_t* g_keys = reinterpret_cast<uint8_t*>(q);
-    uint64_t* g_off = reinterpret_cast<uint64_t*>(q + q_off);
+    const uint64_t kb = offsets[total];
+    DevImage q;  // keys | offsets | created | tombstones | val | data.db | index.db
+    const auto q_keys = q.add<uint8_t>(kb);
+    const auto q_off = q.add<uint64_t>(n + 1);
+    const auto q_cr = q.add<int64_t>(n);
+    const auto q_tb = q.add<uint8_t>(n);
+    const auto q_val = q.add<uint32_t>(n);
+    const auto q_data = q.add<uint8_t>(kb + 17 * n, data);
+    const auto q_idx = q.add<uint8_t>(kb + 8 * n, index);
+    if ((rc = q.alloc(call, kWsCompactOut))) return rc;
+    uint8_t* g_keys = q.ptr(q_keys);
+    uint64_t* g_off = q.ptr(q_off);
     uint64_t gkb = 0;
-    if ((rc = gather_entries(a_keys, a_off, a_cr, a_tb, a_val, d_ids, n, g_keys, kb, g_off,
-                             reinterpret_cast<int64_t*>(q + q_cr), reinterpret_cast<uint8_t*>(q + q_tb),
-                             reinterpret_cast<uint32_t*>(q + q_val), &gkb, s)))
+    if ((rc = gather_entries(m.ptr(m.keys), m.ptr(m.off), m.ptr(m.cr), m.ptr(m.tb), m.ptr(m.val), m.ptr(m.ids), n,
+                             g_keys, kb, g_off, q.ptr(q_cr), q.ptr(q_tb), q.ptr(q_val), &gkb, call.s)))
         return rc;
-    uint8_t* d_data = reinterpret_cast<uint8_t*>(q + q_data);
-    uint8_t* d_idx = reinterpret_cast<uint8_t*>(q + q_idx);
     uint64_t nb = 0;
-    if ((rc = sst_encode(g_keys, g_off, 0, n, reinterpret_cast<const uint32_t*>(q + q_val),
-                         reinterpret_cast<const int64_t*>(q + q_cr), reinterpret_cast<const uint8_t*>(q + q_tb),
-                         data ? d_data : nullptr, kb + 17 * n, data_len, index ? d_idx : nullptr, kb + 8 * n, index_len,
-                         nullptr, 0, &nb, s)))
+    if ((rc = sst_encode(g_keys, g_off, 0, n, q.ptr(q_val), q.ptr(q_cr), q.ptr(q_tb), q.ptr(q_data), kb + 17 * n,
+                         data_len, q.ptr(q_idx), kb + 8 * n, index_len, nullptr, 0, &nb, call.s)))
         return rc;
     *n_out = n;
     if (data && data_cap < *data_len)
@@ -3281,10 +3313,10 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
     vbf_filter* f = nullptr;
     if ((rc = vbf_filter_new(false_positive, n, device, &f))) return rc;
     std::unique_ptr<vbf_filter> hold(f);  // freed on any failure below
-    if ((rc = vbf_filter_set_dev(f, g_keys, g_off, 0, n, 1, s))) return rc;
-    if (data && *data_len) HIP_TRY(hipMemcpyAsync(data, d_data, *data_len, hipMemcpyDeviceToHost, s));
-    if (index && *index_len) HIP_TRY(hipMemcpyAsync(index, d_idx, *index_len, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = vbf_filter_set_dev(f, g_keys, g_off, 0, n, 1, call.s))) return rc;
+    if ((rc = call.down(data, q.ptr(q_data), *data_len)) || (rc = call.down(index, q.ptr(q_idx), *index_len)) ||
+        (rc = call.finish()))
+        return rc;
     *filter_out = hold.release();
     return ok();
 }
@@ -3469,26 +3501,23 @@ int vbf_table_open_host(const uint8_t* data, uint64_t data_len, const uint8_t* i
         if (rc) return rc;
         std::unique_ptr<vbf_table> t(new (std::nothrow) vbf_table());
         if (!t) return table_no_memory();
-        DEVICE_SCOPE(device);
+        HOST_CALL(call, device);
         t->device = device;
-        hipStream_t s;
-        if ((rc = filter_stream(device, &s))) return rc;
-        HostCall turn(device);
-        const uint64_t o_idx = align256(data_len), o_blk = o_idx + align256(index_len);
-        const uint64_t bytes = o_blk + align256(blk.size() * 4);
-        uint8_t* d = nullptr;
+        DevImage img;  // data | index | blocks, owned by the handle
+        const auto p_data = img.add<uint8_t>(data_len, data_len);
+        const auto p_idx = img.add<uint8_t>(index_len, index_len);
+        const auto p_blk = img.add<uint32_t>(blk.size(), !blk.empty());
         if (data_len || index_len) {
-            HIP_TRY(hipMalloc(&t->files, bytes));
-            d = static_cast<uint8_t*>(t->files);
-            if (data_len) HIP_TRY(hipMemcpyAsync(d, data, data_len, hipMemcpyHostToDevice, s));
-            if (index_len) HIP_TRY(hipMemcpyAsync(d + o_idx, index, index_len, hipMemcpyHostToDevice, s));
-            if (!blk.empty())
-                HIP_TRY(hipMemcpyAsync(d + o_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));  // pageable sources
+            HIP_TRY(hipMalloc(&t->files, img.bytes));
+            img.base = t->files;
+            if ((rc = call.up(img.ptr(p_data), data, data_len)) || (rc = call.up(img.ptr(p_idx), index, index_len)) ||
+                (rc = call.up(img.ptr(p_blk), blk.data(), blk.size())) || (rc = call.sync()))  // pageable sources
+                return rc;
         }
-        rc = table_open(*t, data_len ? d : nullptr, data_len, index_len ? d + o_idx : nullptr, index_len,
-                        blk.empty() ? nullptr : reinterpret_cast<const uint32_t*>(d + o_blk), blk.size(), s);
-        if (rc) return rc;
+        if ((rc = table_open(*t, img.ptr(p_data), data_len, img.ptr(p_idx), index_len, img.ptr(p_blk), blk.size(),
+                             call.s)))
+            return rc;
+        call.settled();  // table_open returned synchronised
         *out = t.release();
     } catch (const std::bad_alloc&) {
         return table_no_memory();
@@ -3570,31 +3599,23 @@ int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t st
                 if (filters[i]->bits->device != device)
                     return fail(VBF_EINVAL, "filters[%u] lives on device %d, the tables on %d", i,
                                 filters[i]->bits->device, device);
-        DEVICE_SCOPE(device);
-        hipStream_t s;
-        if ((rc = filter_stream(device, &s))) return rc;
-        HostCall turn(device);
-        const uint64_t kbytes = offsets ? offsets[n] - offsets[0] : n * stride;
-        const uint64_t o_off = align256(kbytes), o_cand = o_off + align256(offsets ? (n + 1) * 8 : 0);
-        const uint64_t o_found = o_cand + align256(filters ? n * nsst : 0), o_idx = o_found + align256(n);
-        const uint64_t o_val = o_idx + align256(n * 4), o_cr = o_val + align256(n * 4);
-        void* ws = nullptr;
-        if ((rc = get_workspace(s, o_cr + n * 8, &ws, kWsTableIO))) return rc;
-        uint8_t* d_keys = static_cast<uint8_t*>(ws);
-        uint64_t* d_off = offsets ? reinterpret_cast<uint64_t*>(d_keys + o_off) : nullptr;
-        uint8_t* d_cand = filters ? d_keys + o_cand : nullptr;
-        uint8_t* d_found = found ? d_keys + o_found : nullptr;
-        uint32_t* d_idx = table_idx ? reinterpret_cast<uint32_t*>(d_keys + o_idx) : nullptr;
-        uint32_t* d_val = val_offsets ? reinterpret_cast<uint32_t*>(d_keys + o_val) : nullptr;
-        uint64_t* d_cr = created_ms ? reinterpret_cast<uint64_t*>(d_keys + o_cr) : nullptr;
-        if (kbytes) HIP_TRY(hipMemcpyAsync(d_keys, keys + (offsets ? offsets[0] : 0), kbytes, hipMemcpyHostToDevice, s));
-        if (offsets) {  // rebased to absolute positions in the device copy
-            std::vector<uint64_t> o(offsets, offsets + n + 1);
-            const uint64_t b0 = o[0];
-            for (auto& x : o) x -= b0;
-            HIP_TRY(hipMemcpyAsync(d_off, o.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));
-        }
+        HOST_CALL(call, device);
+        const uint64_t k0 = offsets ? offsets[0] : 0, kbytes = offsets ? offsets[n] - k0 : n * stride;
+        DevImage img;  // keys | offsets | candidates | found | table_idx | val_offsets | created
+        const auto p_keys = img.add<uint8_t>(kbytes);
+        const auto p_off = img.add<uint64_t>(n + 1, offsets);
+        const auto p_cand = img.add<uint8_t>(n * nsst, filters);
+        const auto p_found = img.add<uint8_t>(n, found);
+        const auto p_idx = img.add<uint32_t>(n, table_idx);
+        const auto p_val = img.add<uint32_t>(n, val_offsets);
+        const auto p_cr = img.add<uint64_t>(n, created_ms);
+        if ((rc = img.alloc(call, kWsTableIO))) return rc;
+        uint8_t* d_keys = img.ptr(p_keys);
+        uint64_t* d_off = img.ptr(p_off);
+        uint8_t* d_cand = img.ptr(p_cand);
+        if ((rc = call.up(d_keys, kbytes ? keys + k0 : nullptr, kbytes))) return rc;
+        // absolute positions in the device copy
+        if (offsets && ((rc = call.up_rebased(d_off, offsets, n + 1)) || (rc = call.sync()))) return rc;
         if (filters) {  // filter_sstables_by_key_range (range.rs:91-147) with the tables' own key ranges
             std::vector<uint8_t> bounds;
             std::vector<uint64_t> boff(1, 0);
@@ -3605,16 +3626,16 @@ int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t st
                 boff.push_back(bounds.size());
             }
             bounds.push_back(0);  // never NULL
-            if ((rc = multi_probe(d_keys, d_off, stride, n, 1, nsst, filters, bounds.data(), boff.data(), d_cand, s)))
+            if ((rc = multi_probe(d_keys, d_off, stride, n, 1, nsst, filters, bounds.data(), boff.data(), d_cand, call.s)))
                 return rc;
         }
-        if ((rc = table_lookup(d_keys, d_off, stride, n, nsst, tables, d_cand, d_found, d_idx, d_val, d_cr, s)))
+        if ((rc = table_lookup(d_keys, d_off, stride, n, nsst, tables, d_cand, img.ptr(p_found), img.ptr(p_idx),
+                               img.ptr(p_val), img.ptr(p_cr), call.s)))
             return rc;
-        if (found) HIP_TRY(hipMemcpyAsync(found, d_found, n, hipMemcpyDeviceToHost, s));
-        if (table_idx) HIP_TRY(hipMemcpyAsync(table_idx, d_idx, n * 4, hipMemcpyDeviceToHost, s));
-        if (val_offsets) HIP_TRY(hipMemcpyAsync(val_offsets, d_val, n * 4, hipMemcpyDeviceToHost, s));
-        if (created_ms) HIP_TRY(hipMemcpyAsync(created_ms, d_cr, n * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        if ((rc = call.down(found, img.ptr(p_found), n)) || (rc = call.down(table_idx, img.ptr(p_idx), n)) ||
+            (rc = call.down(val_offsets, img.ptr(p_val), n)) || (rc = call.down(created_ms, img.ptr(p_cr), n)) ||
+            (rc = call.finish()))
+            return rc;
     } catch (const std::bad_alloc&) {
         return table_no_memory();
     }
@@ -3818,50 +3839,44 @@ int vbf_table_scan_host(const uint8_t* bounds, const uint64_t* bounds_off, uint6
     }
     const int device = tables[0]->device;
     try {
-        DEVICE_SCOPE(device);
-        hipStream_t s;
-        if ((rc = filter_stream(device, &s))) return rc;
-        HostCall turn(device);
+        HOST_CALL(call, device);
         // bounds and their offsets, rebased to positions in the device copy
         const uint64_t b0 = bounds_off[0], bbytes = bounds_off[2 * nranges] - b0;
-        const uint64_t o_boff = align256(bbytes);
-        void* ws = nullptr;
-        if ((rc = get_workspace(s, o_boff + (2 * nranges + 1) * 8, &ws, kWsTableScanIO))) return rc;
-        uint8_t* d_bounds = static_cast<uint8_t*>(ws);
-        uint64_t* d_boff = reinterpret_cast<uint64_t*>(d_bounds + o_boff);
-        std::vector<uint64_t> boff(bounds_off, bounds_off + 2 * nranges + 1);
-        for (auto& x : boff) x -= b0;
-        if (bbytes) HIP_TRY(hipMemcpyAsync(d_bounds, bounds + b0, bbytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_boff, boff.data(), boff.size() * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));  // pageable sources
+        DevImage in;
+        const auto p_bounds = in.add<uint8_t>(bbytes);
+        const auto p_boff = in.add<uint64_t>(2 * nranges + 1);
+        if ((rc = in.alloc(call, kWsTableScanIO))) return rc;
+        if ((rc = call.up(in.ptr(p_bounds), bbytes ? bounds + b0 : nullptr, bbytes)) ||
+            (rc = call.up_rebased(in.ptr(p_boff), bounds_off, 2 * nranges + 1)) || (rc = call.sync()))  // pageable sources
+            return rc;
         vbf::TableScanArgs a;
-        if ((rc = table_scan_sizes(d_bounds, d_boff, nranges, nsst, tables, flags, s, &a, n_out, key_bytes)))
+        if ((rc = table_scan_sizes(in.ptr(p_bounds), in.ptr(p_boff), nranges, nsst, tables, flags, call.s, &a,
+                                   n_out, key_bytes)))
             return rc;
         if ((rc = table_scan_caps(o, entries_cap, keys_cap, *n_out, *key_bytes))) return rc;
-        if (!o.any()) return ok();
+        if (!o.any()) {  // the size query: table_scan_sizes returned synchronised
+            call.settled();
+            return ok();
+        }
         // the outputs' device staging; the bounds (same slot) were consumed before the sizes came back
         const uint64_t n = *n_out, kb = *key_bytes;
-        const uint64_t o_koff = align256((nranges + 1) * 8), o_cr = o_koff + align256((n + 1) * 8);
-        const uint64_t o_idx = o_cr + align256(n * 8), o_val = o_idx + align256(n * 4);
-        const uint64_t o_tomb = o_val + align256(n * 4), o_keys = o_tomb + align256(n);
-        if ((rc = get_workspace(s, o_keys + kb, &ws, kWsTableScanIO))) return rc;
-        char* ob = static_cast<char*>(ws);
-        const ScanOut d{range_off ? reinterpret_cast<uint64_t*>(ob) : nullptr,
-                        keys ? reinterpret_cast<uint8_t*>(ob + o_keys) : nullptr,
-                        key_off ? reinterpret_cast<uint64_t*>(ob + o_koff) : nullptr,
-                        table_idx ? reinterpret_cast<uint32_t*>(ob + o_idx) : nullptr,
-                        val_offsets ? reinterpret_cast<uint32_t*>(ob + o_val) : nullptr,
-                        created_ms ? reinterpret_cast<uint64_t*>(ob + o_cr) : nullptr,
-                        tombstones ? reinterpret_cast<uint8_t*>(ob + o_tomb) : nullptr};
-        if ((rc = table_scan_fill(a, d, s))) return rc;
-        if (range_off) HIP_TRY(hipMemcpyAsync(range_off, d.range_off, (nranges + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (key_off) HIP_TRY(hipMemcpyAsync(key_off, d.key_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (keys && kb) HIP_TRY(hipMemcpyAsync(keys, d.keys, kb, hipMemcpyDeviceToHost, s));
-        if (table_idx && n) HIP_TRY(hipMemcpyAsync(table_idx, d.table_idx, n * 4, hipMemcpyDeviceToHost, s));
-        if (val_offsets && n) HIP_TRY(hipMemcpyAsync(val_offsets, d.val_offsets, n * 4, hipMemcpyDeviceToHost, s));
-        if (created_ms && n) HIP_TRY(hipMemcpyAsync(created_ms, d.created_ms, n * 8, hipMemcpyDeviceToHost, s));
-        if (tombstones && n) HIP_TRY(hipMemcpyAsync(tombstones, d.tombstones, n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        DevImage out;
+        const auto p_roff = out.add<uint64_t>(nranges + 1, range_off);
+        const auto p_koff = out.add<uint64_t>(n + 1, key_off);
+        const auto p_cr = out.add<uint64_t>(n, created_ms);
+        const auto p_idx = out.add<uint32_t>(n, table_idx);
+        const auto p_val = out.add<uint32_t>(n, val_offsets);
+        const auto p_tomb = out.add<uint8_t>(n, tombstones);
+        const auto p_keys = out.add<uint8_t>(kb, keys);
+        if ((rc = out.alloc(call, kWsTableScanIO))) return rc;
+        const ScanOut d{out.ptr(p_roff), out.ptr(p_keys), out.ptr(p_koff), out.ptr(p_idx),
+                        out.ptr(p_val),  out.ptr(p_cr),   out.ptr(p_tomb)};
+        if ((rc = table_scan_fill(a, d, call.s))) return rc;
+        if ((rc = call.down(range_off, d.range_off, nranges + 1)) || (rc = call.down(key_off, d.key_off, n + 1)) ||
+            (rc = call.down(keys, d.keys, kb)) || (rc = call.down(table_idx, d.table_idx, n)) ||
+            (rc = call.down(val_offsets, d.val_offsets, n)) || (rc = call.down(created_ms, d.created_ms, n)) ||
+            (rc = call.down(tombstones, d.tombstones, n)) || (rc = call.finish()))
+            return rc;
     } catch (const std::bad_alloc&) {
         return table_no_memory();
     }
@@ -4040,19 +4055,16 @@ int vbf_vlog_open_host(const uint8_t* bytes, uint64_t len, uint64_t base, int de
     if (rc) return rc;
     std::unique_ptr<vbf_vlog> v(new (std::nothrow) vbf_vlog());
     if (!v) return table_no_memory();
-    DEVICE_SCOPE(device);
+    HOST_CALL(call, device);
     v->device = device;
     v->len = len;
     v->base = base;
     if (len) {
-        hipStream_t s;
-        if ((rc = filter_stream(device, &s))) return rc;
-        HostCall turn(device);
         HIP_TRY(hipMalloc(&v->owned, len));
-        HIP_TRY(hipMemcpyAsync(v->owned, bytes, len, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));  // a pageable source
+        if ((rc = call.up(static_cast<uint8_t*>(v->owned), bytes, len)) || (rc = call.sync())) return rc;  // a pageable source
         v->bytes = static_cast<const uint8_t*>(v->owned);
     }
+    call.settled();
     *out = v.release();
     return ok();
 }
@@ -4099,47 +4111,37 @@ int vbf_vlog_get_host(const vbf_vlog* v, const uint32_t* val_offsets, const uint
         return ok();
     }
     try {
-        const int device = v->device;
-        DEVICE_SCOPE(device);
-        hipStream_t s;
-        if ((rc = filter_stream(device, &s))) return rc;
-        HostCall turn(device);
+        HOST_CALL(call, v->device);
         const uint64_t k0 = keys && offsets ? offsets[0] : 0;
         const uint64_t kb = !keys ? 0 : (offsets ? offsets[n] - k0 : n * stride);
-        const uint64_t o_found = align256(n * 4), o_keys = o_found + align256(found ? n : 0);
-        const uint64_t o_off = o_keys + align256(kb + 1);
-        void* ws = nullptr;
-        if ((rc = get_workspace(s, o_off + (keys && offsets ? (n + 1) * 8 : 0), &ws, kWsVlogIO))) return rc;
-        char* b = static_cast<char*>(ws);
-        std::vector<uint64_t> o;
-        HIP_TRY(hipMemcpyAsync(b, val_offsets, n * 4, hipMemcpyHostToDevice, s));
-        if (found) HIP_TRY(hipMemcpyAsync(b + o_found, found, n, hipMemcpyHostToDevice, s));
-        if (kb) HIP_TRY(hipMemcpyAsync(b + o_keys, keys + k0, kb, hipMemcpyHostToDevice, s));
-        if (keys && offsets) {  // rebased to positions in the device copy
-            o.assign(offsets, offsets + n + 1);
-            for (auto& x : o) x -= k0;
-            HIP_TRY(hipMemcpyAsync(b + o_off, o.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-        }
+        DevImage img;  // val_offsets | found | keys | offsets
+        const auto p_vo = img.add<uint32_t>(n);
+        const auto p_found = img.add<uint8_t>(n, found);
+        const auto p_keys = img.add<uint8_t>(kb + 1, keys);
+        const auto p_off = img.add<uint64_t>(n + 1, keys && offsets);
+        if ((rc = img.alloc(call, kWsVlogIO))) return rc;
+        if ((rc = call.up(img.ptr(p_vo), val_offsets, n)) || (rc = call.up(img.ptr(p_found), found, n)) ||
+            (rc = call.up(img.ptr(p_keys), kb ? keys + k0 : nullptr, kb)))
+            return rc;
+        // positions in the device copy
+        if (p_off.present && (rc = call.up_rebased(img.ptr(p_off), offsets, n + 1))) return rc;
         vbf::VlogGetArgs a;
         uint64_t total = 0;
-        rc = vlog_get_sizes(v, reinterpret_cast<const uint32_t*>(b), found ? reinterpret_cast<const uint8_t*>(b + o_found) : nullptr,
-                            n, keys ? reinterpret_cast<const uint8_t*>(b + o_keys) : nullptr,
-                            keys && offsets ? reinterpret_cast<const uint64_t*>(b + o_off) : nullptr, stride, s, &a, &total);
-        if (rc) {
-            (void)hipStreamSynchronize(s);  // the uploads read the caller's buffers
+        if ((rc = vlog_get_sizes(v, img.ptr(p_vo), img.ptr(p_found), n, img.ptr(p_keys), img.ptr(p_off), stride,
+                                 call.s, &a, &total)))
             return rc;
-        }
         *value_bytes = total;
         if ((rc = vlog_values_cap(values, values_cap, total))) return rc;
-        if (status) HIP_TRY(hipMemcpyAsync(status, a.status, n, hipMemcpyDeviceToHost, s));
-        if (value_off) HIP_TRY(hipMemcpyAsync(value_off, a.voff, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+        if ((rc = call.down(status, a.status, n)) || (rc = call.down(value_off, a.voff, n + 1))) return rc;
         if (values && total) {
-            void* d_values = nullptr;
-            if ((rc = get_workspace(s, total, &d_values, kWsVlogOut))) return rc;
-            if ((rc = vlog_get_fill(a, static_cast<uint8_t*>(d_values), s))) return rc;
-            HIP_TRY(hipMemcpyAsync(values, d_values, total, hipMemcpyDeviceToHost, s));
+            DevImage vals;
+            const auto p_values = vals.add<uint8_t>(total);
+            if ((rc = vals.alloc(call, kWsVlogOut))) return rc;
+            if ((rc = vlog_get_fill(a, vals.ptr(p_values), call.s)) ||
+                (rc = call.down(values, vals.ptr(p_values), total)))
+                return rc;
         }
-        HIP_TRY(hipStreamSynchronize(s));
+        if ((rc = call.finish())) return rc;
     } catch (const std::bad_alloc&) {
         return table_no_memory();
     }
@@ -4216,43 +4218,38 @@ int vbf_vlog_encode_host(const uint8_t* keys, const uint64_t* offsets, uint64_t 
     const uint64_t vo[3] = {value_off[0], value_off[n - 1], value_off[n]};
     if ((rc = vlog_enc_plan(&a, ko, vo, out, out_cap, out_len))) return rc;
     if (!out && !val_offsets) return ok();  // the size query needs no device
-    DEVICE_SCOPE(device);
-    hipStream_t s;
-    if ((rc = filter_stream(device, &s))) return rc;
-    HostCall turn(device);
+    HOST_CALL(call, device);
     // device image: keys | offsets | values | value_off | created | tombstones | val_offsets | out
     const uint64_t kb = ko[2] - ko[0], vb = vo[2] - vo[0];
-    const uint64_t o_off = align256(kb), o_val = o_off + align256(offsets ? (n + 1) * 8 : 0);
-    const uint64_t o_voff = o_val + align256(vb), o_cr = o_voff + align256((n + 1) * 8);
-    const uint64_t o_tb = o_cr + align256(created_ms ? n * 8 : 0), o_vo = o_tb + align256(tombstones ? n : 0);
-    const uint64_t o_out = o_vo + align256(val_offsets ? n * 4 : 0);
-    void* ws = nullptr;
-    if ((rc = get_workspace(s, o_out + (out ? a.total : 0), &ws, kWsVlogEncIO))) return rc;
-    char* b = static_cast<char*>(ws);
-    if (kb) HIP_TRY(hipMemcpyAsync(b, keys + ko[0], kb, hipMemcpyHostToDevice, s));
-    if (offsets) HIP_TRY(hipMemcpyAsync(b + o_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (vb) HIP_TRY(hipMemcpyAsync(b + o_val, values + vo[0], vb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b + o_voff, value_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (created_ms) HIP_TRY(hipMemcpyAsync(b + o_cr, created_ms, n * 8, hipMemcpyHostToDevice, s));
-    if (tombstones) HIP_TRY(hipMemcpyAsync(b + o_tb, tombstones, n, hipMemcpyHostToDevice, s));
+    DevImage img;
+    const auto p_keys = img.add<uint8_t>(kb);
+    const auto p_off = img.add<uint64_t>(n + 1, offsets);
+    const auto p_val = img.add<uint8_t>(vb);
+    const auto p_voff = img.add<uint64_t>(n + 1);
+    const auto p_cr = img.add<int64_t>(n, created_ms);
+    const auto p_tb = img.add<uint8_t>(n, tombstones);
+    const auto p_vo = img.add<uint32_t>(n, val_offsets);
+    const auto p_out = img.add<uint8_t>(a.total, out);
+    if ((rc = img.alloc(call, kWsVlogEncIO))) return rc;
+    if ((rc = call.up(img.ptr(p_keys), kb ? keys + ko[0] : nullptr, kb)) ||
+        (rc = call.up(img.ptr(p_off), offsets, n + 1)) ||
+        (rc = call.up(img.ptr(p_val), vb ? values + vo[0] : nullptr, vb)) ||
+        (rc = call.up(img.ptr(p_voff), value_off, n + 1)) || (rc = call.up(img.ptr(p_cr), created_ms, n)) ||
+        (rc = call.up(img.ptr(p_tb), tombstones, n)))
+        return rc;
     // both offset arrays hold absolute positions: the device copies start at keys + offsets[0] and
     // values + value_off[0]
-    a.keys = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(b) - ko[0]);
-    a.values = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(b + o_val) - vo[0]);
-    a.offsets = offsets ? reinterpret_cast<const uint64_t*>(b + o_off) : nullptr;
-    a.value_off = reinterpret_cast<const uint64_t*>(b + o_voff);
-    a.created = created_ms ? reinterpret_cast<const int64_t*>(b + o_cr) : nullptr;
-    a.tomb = tombstones ? reinterpret_cast<const uint8_t*>(b + o_tb) : nullptr;
-    a.val_offsets = val_offsets ? reinterpret_cast<uint32_t*>(b + o_vo) : nullptr;
-    a.out = out ? reinterpret_cast<uint8_t*>(b + o_out) : nullptr;
-    if ((rc = vlog_enc_emit(a, s))) {
-        (void)hipStreamSynchronize(s);  // the uploads read the caller's buffers
-        return rc;
-    }
-    if (out && a.total) HIP_TRY(hipMemcpyAsync(out, a.out, a.total, hipMemcpyDeviceToHost, s));
-    if (val_offsets) HIP_TRY(hipMemcpyAsync(val_offsets, a.val_offsets, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ok();
+    a.keys = arena_base(img.ptr(p_keys), ko[0]);
+    a.values = arena_base(img.ptr(p_val), vo[0]);
+    a.offsets = img.ptr(p_off);
+    a.value_off = img.ptr(p_voff);
+    a.created = img.ptr(p_cr);
+    a.tomb = img.ptr(p_tb);
+    a.val_offsets = img.ptr(p_vo);
+    a.out = img.ptr(p_out);
+    if ((rc = vlog_enc_emit(a, call.s))) return rc;
+    if ((rc = call.down(out, a.out, a.total)) || (rc = call.down(val_offsets, a.val_offsets, n))) return rc;
+    return call.finish();
 }
 
 }  // extern "C"
