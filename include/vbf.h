@@ -42,6 +42,11 @@
  *   DataStore::get_value_from_vlog     src/db/store.rs:628-641     -> vbf_vlog_get_* (tombstone -> no value)
  *   ValueLog::append                   src/vlog/v_log.rs:173-196   -> vbf_vlog_encode_* (val_offsets)
  *   ValueLogEntry::serialize           src/vlog/v_log.rs:291-309   -> vbf_vlog_encode_* (the bytes)
+ *   MemTable::insert (the SkipMap)     src/memtable/mem.rs:207-221 -> vbf_memtable_sort_* (last put wins)
+ *   MemTable::insert (contains, set)   src/memtable/mem.rs:209-211 -> vbf_filter_insert_host / _dev
+ *   Flusher::flush                     src/flush/flusher.rs:37-64  -> vbf_flush_write_host
+ *   Table::write_to_file (a memtable)  src/sst/table.rs:258-326    -> vbf_flush_write_host
+ *   DataStore::put (log, then insert)  src/db/store.rs:215-243     -> vbf_vlog_encode_* + vbf_flush_write_host
  *
  * Key batches.  `keys` holds the key bytes back to back.  When `offsets` is non-NULL it has
  * n+1 nondecreasing entries and key j is keys[offsets[j] .. offsets[j+1]) (positions are
@@ -62,7 +67,8 @@
  * shares its staging: vbf_build_host, vbf_probe_host and the filters' set_host / contains_host /
  * words copies take turns on the device's two staging streams, and the other `_host` entry points
  * (sst_decode, sst_encode, rebuild_from_sst, multi_probe, compact_merge, compact_write,
- * table_open, table_get, table_scan, vlog_open, vlog_get, vlog_encode) take turns on its shared
+ * table_open, table_get, table_scan, vlog_open, vlog_get, vlog_encode, memtable_sort,
+ * flush_write, and filter_insert_host on a device-resident filter) take turns on its shared
  * stream, each from its first upload to its last download; the two groups overlap each other, and
  * devices never wait for each other.  A call that spans several devices (vbf_multi_probe_host over filters on several GPUs)
  * holds one device at a time.  Locks are taken filters first (in address order), then the device.
@@ -105,7 +111,8 @@ int vbf_device_count(int* count);
  * 15 encode table scan + block count, 16 index.db emit, 17 data.db emit, 18 table open (side
  * tables + validation), 19 table get, 20 table scan bounds + rank (with their scans), 21 table scan
  * emit + key copy, 22 value-log fetch sizes + scan, 23 value-log fetch copy, 24 value-log encode
- * (its check and its copy).
+ * (its check and its copy), 25 memtable tile sort (with its prefix pass), 26 memtable merge levels
+ * + keep flags + select, 27 filter insert (count passes and the build).
  * vbf_profile_read synchronizes, returns per-phase summed ms and launch counts, and resets; it
  * fills the first `nphases` phases, so a caller built against a shorter list keeps working (the
  * later phases' records are dropped). */
@@ -550,6 +557,65 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
                            vbf_filter** filter_out, uint8_t* data, uint64_t data_cap, uint64_t* data_len,
                            uint8_t* index, uint64_t index_cap, uint64_t* index_len, uint64_t* n_out,
                            uint32_t* upd_ids, int64_t* upd_time, uint64_t* n_upd, int device);
+
+/* ---- memtable flush: a batch of puts in arrival order -> an SST's files ----
+ *
+ * DataStore::put appends to the value log and calls MemTable::insert (src/db/store.rs:215-243,
+ * src/memtable/mem.rs:207-221); Flusher::flush hands the memtable's SkipMap to
+ * Table::write_to_file (src/flush/flusher.rs:37-64, src/sst/table.rs:258-326).  These entry points
+ * are that data transformation for a whole batch -- a bulk load, or the replay of a recovered value
+ * log (src/db/recovery.rs:245-286).  Cutting a put stream into memtables by capacity (is_full,
+ * mem.rs:277-279), the `head` entry of migrate_memtable_to_read_only (store.rs:250-263; a caller
+ * appends it to the batch), summary.db and file I/O stay with the caller.
+ *
+ * vbf_memtable_sort_*: the outcome of SkipMap::insert(key_j, ..) for j = 0 .. n-1 in order.
+ * crossbeam-skiplist 0.1.3 removes an entry of the same key before it inserts, so the last insert
+ * of a key wins whatever its created_at.  out_ids (capacity n) receives the distinct keys in
+ * ascending `Ord for [u8]` order (unsigned bytes, a proper prefix first, the empty key first of
+ * all), each represented by the largest j that holds it; *n_out = their number.  n == 0 is VBF_OK
+ * with *n_out = 0 and no device work; n > 2^31 - 1 is VBF_EINVAL ("too many entries") before any.
+ * Descending offsets are VBF_EINVAL: _host finds them on the host, _dev after its first pass (no
+ * later pass reads a key of such a batch).  _dev synchronises the stream once, to read the count;
+ * its workspace (33 bytes per entry) is cached per stream. */
+int vbf_memtable_sort_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                          uint32_t* out_ids, uint64_t* n_out, void* stream);
+int vbf_memtable_sort_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                           uint32_t* out_ids, uint64_t* n_out, int device);
+
+/* MemTable::insert's filter step, `if !contains(key) { set(key) }` (mem.rs:209-211), replayed over
+ * the batch in order against the filter's current bits.  The bits end as a set of every key would
+ * leave them (a skipped set would have changed nothing); no_of_elements grows only by the keys
+ * that were not contained when their turn came (u32, wrapping), and that number is returned in
+ * *n_new (may be NULL).  It is the count filter.db stores for a flushed SST, from which recovery
+ * recomputes m (bf.rs:144-147).  k == 0: every key is contained, *n_new = 0.  m == 0 with k > 0 is
+ * VBF_EDIVZERO.  n <= 2^32 - 2.  A device-resident filter takes one u32 of scratch per bit, so
+ * m <= 2^30 bits (VBF_EINVAL beyond, whatever the residency, before any work).  _host runs the
+ * literal loop on the CPU for a host-resident filter; _dev needs a device-resident one and
+ * synchronises the stream once, for the count.  Ordered by the filter's lock like set_host /
+ * set_dev. */
+int vbf_filter_insert_host(vbf_filter* f, const uint8_t* keys, const uint64_t* offsets, uint64_t stride,
+                           uint64_t n, int len_prefix, uint64_t* n_new);
+int vbf_filter_insert_dev(vbf_filter* f, const uint8_t* keys, const uint64_t* offsets, uint64_t stride,
+                          uint64_t n, int len_prefix, uint64_t* n_new, void* stream);
+
+/* One batch of puts carried through to what Table::write_to_file writes, the counterpart of
+ * vbf_compact_write_host: one upload, vbf_memtable_sort, the gather of the surviving entries with
+ * their per-entry arrays (val_offsets / created_ms / tombstones, each may be NULL: zeros), the
+ * data.db / index.db encode and, when `filter` is non-NULL, vbf_filter_insert over all n keys in
+ * input order (len_prefix = 1), with nothing returned to the host in between.  `filter` must be
+ * device-resident on `device` (a caller flushing a real memtable owns its host filter and passes
+ * NULL); it is touched only when everything before it succeeded.  out_ids (may be NULL, capacity
+ * n) receives the sort's ids: keys[out_ids[0]] is the summary's smallest key and
+ * keys[out_ids[*n_out - 1]] its biggest (table.rs:270-274).  *data_len / *index_len / *n_out are
+ * always written; data / index may be NULL (a size query), and a capacity that is too small is
+ * VBF_EINVAL with the sizes written and no output touched.  Key bytes + 17 n and + 8 n always
+ * suffice.  n == 0 is VBF_EINVAL with zero sizes ("Cannot flush an empty table",
+ * flusher.rs:40-44); a key of more than 4079 bytes is the encoder's VBF_EINVAL.  Synchronous. */
+int vbf_flush_write_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                         const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones,
+                         vbf_filter* filter, uint8_t* data, uint64_t data_cap, uint64_t* data_len,
+                         uint8_t* index, uint64_t index_cap, uint64_t* index_len, uint32_t* out_ids,
+                         uint64_t* n_out, int device);
 
 /* ---- batched point lookups in SST tables ----
  * The read path after the filters: per key and candidate SST the reference scans index.db for the

@@ -148,6 +148,12 @@ SIGNATURES = {
                                     _vp, _vp]),
     "vbf_vlog_encode_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64),
                                      _vp, _int]),
+    "vbf_memtable_sort_dev": (_int, [_vp, _vp, _u64, _u64, _vp, ctypes.POINTER(_u64), _vp]),
+    "vbf_memtable_sort_host": (_int, [_vp, _vp, _u64, _u64, _vp, ctypes.POINTER(_u64), _int]),
+    "vbf_filter_insert_host": (_int, [_vp, _vp, _vp, _u64, _u64, _int, ctypes.POINTER(_u64)]),
+    "vbf_filter_insert_dev": (_int, [_vp, _vp, _vp, _u64, _u64, _int, ctypes.POINTER(_u64), _vp]),
+    "vbf_flush_write_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64,
+                                     ctypes.POINTER(_u64), _vp, ctypes.POINTER(_u64), _int]),
 }
 
 
@@ -201,7 +207,7 @@ def device_count():
 PHASES = ("tile_sort", "transpose", "seg_or", "atomic_build", "probe", "sst_walk", "sst_scan", "sst_emit",
           "merge_levels", "fold", "select", "probe_pack", "probe_seg", "probe_out", "enc_tile", "enc_scan",
           "enc_index", "enc_data", "table_open", "table_get", "scan_rank", "scan_emit", "vlog_sizes", "vlog_copy",
-          "vlog_encode")
+          "vlog_encode", "mem_sort", "mem_merge", "filter_insert")
 
 
 def profile_read():

@@ -174,6 +174,11 @@ enum WsSlot {
     kWsVlogOut = 23,
     kWsVlogEnc = 24,
     kWsVlogEncIO = 25,
+    kWsMemSort = 26,
+    kWsMemIO = 27,
+    kWsMemOut = 28,
+    kWsFilterInsert = 29,
+    kWsFilterInsertIO = 30,
 };
 struct Workspace {
     int device;
@@ -3007,6 +3012,37 @@ int compact_validate(const uint64_t* offsets, const int64_t* created, const uint
     return VBF_OK;
 }
 
+// The merge levels over first-level segments [bnd[i], bnd[i + 1]): per level the segment
+// boundaries (`all`) and every pair's first tile (`tiles_all`), in the layout merge_levels_from
+// walks.  No level for a single segment.
+struct MergeGeometry {
+    std::vector<uint64_t> all, tiles_all, ntiles_lv;
+    std::vector<uint32_t> nseg_lv;
+    uint64_t max_tiles = 1;
+    explicit MergeGeometry(std::vector<uint64_t> bnd) {
+        const uint64_t tile = vbf::compact_tile();
+        uint32_t nseg = (uint32_t)bnd.size() - 1;
+        while (nseg > 1) {
+            all.insert(all.end(), bnd.begin(), bnd.end());
+            nseg_lv.push_back(nseg);
+            uint64_t t = 0;
+            for (uint32_t i = 0; i < nseg; i += 2) {
+                tiles_all.push_back(t);
+                const uint64_t len = bnd[std::min(i + 2, nseg)] - bnd[i];
+                t += (len + tile - 1) / tile;
+            }
+            tiles_all.push_back(t);
+            ntiles_lv.push_back(t);
+            max_tiles = std::max(max_tiles, t);
+            std::vector<uint64_t> nb;
+            for (uint32_t i = 0; i < nseg; i += 2) nb.push_back(bnd[i]);
+            nb.push_back(bnd[nseg]);
+            bnd.swap(nb);
+            nseg = (uint32_t)bnd.size() - 1;
+        }
+    }
+};
+
 int compact_merge(const uint8_t* keys, const uint64_t* offsets, const int64_t* created, const uint8_t* tomb,
                   const uint64_t* run_off, uint32_t nruns, const uint8_t* map_keys, const uint64_t* map_off,
                   const int64_t* map_time, uint64_t map_n, int use_ttl, uint64_t entry_ttl_ms, uint64_t tomb_ttl_ms,
@@ -3021,30 +3057,12 @@ int compact_merge(const uint8_t* keys, const uint64_t* offsets, const int64_t* c
     if (rc) return rc;
     if (total == 0) return VBF_OK;
     // merge levels: segment boundaries and per-pair tile starts per level, all uploaded at once
-    const uint64_t tile = vbf::compact_tile();
-    std::vector<uint64_t> bnd(run_off, run_off + nruns + 1);
-    std::vector<uint64_t> all, tiles_all, ntiles_lv;
-    std::vector<uint32_t> nseg_lv;
-    uint64_t max_tiles = 1;
-    uint32_t nseg = nruns;
-    while (nseg > 1) {
-        all.insert(all.end(), bnd.begin(), bnd.end());
-        nseg_lv.push_back(nseg);
-        uint64_t t = 0;
-        for (uint32_t i = 0; i < nseg; i += 2) {
-            tiles_all.push_back(t);
-            const uint64_t len = bnd[std::min(i + 2, nseg)] - bnd[i];
-            t += (len + tile - 1) / tile;
-        }
-        tiles_all.push_back(t);
-        ntiles_lv.push_back(t);
-        max_tiles = std::max(max_tiles, t);
-        std::vector<uint64_t> nb;
-        for (uint32_t i = 0; i < nseg; i += 2) nb.push_back(bnd[i]);
-        nb.push_back(bnd[nseg]);
-        bnd.swap(nb);
-        nseg = (uint32_t)bnd.size() - 1;
-    }
+    const MergeGeometry geo(std::vector<uint64_t>(run_off, run_off + nruns + 1));
+    const std::vector<uint64_t>& all = geo.all;
+    const std::vector<uint64_t>& tiles_all = geo.tiles_all;
+    const std::vector<uint64_t>& ntiles_lv = geo.ntiles_lv;
+    const std::vector<uint32_t>& nseg_lv = geo.nseg_lv;
+    const uint64_t max_tiles = geo.max_tiles;
     size_t t1 = 0, t2 = 0, t3 = 0;
     HIP_TRY(vbf::select_u32(nullptr, &t1, nullptr, nullptr, nullptr, nullptr, total, s));
     HIP_TRY(vbf::select_i64(nullptr, &t2, nullptr, nullptr, nullptr, nullptr, total, s));
@@ -3319,6 +3337,342 @@ int vbf_compact_write_host(const uint8_t* keys, const uint64_t* offsets, const i
         return rc;
     *filter_out = hold.release();
     return ok();
+}
+
+}  // extern "C"
+
+// ---- memtable flush: MemTable::insert's order and filter step, Flusher::flush (vbf_memtable.hip) ----
+
+namespace {
+
+// vbf_filter_insert_*: one u32 of scratch per filter bit, so at most 2^30 bits (4 GiB).
+constexpr uint64_t kInsertMaxBits = 1ull << 30;
+
+// Shared by the _dev and _host sorts, before any device work.  The entry limit first, as in the
+// merge: a count that large is wrong whatever the pointers are.
+int memtable_check(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, const uint32_t* out_ids,
+                   uint64_t* n_out) {
+    if (!n_out) return fail(VBF_EINVAL, "n_out is NULL");
+    *n_out = 0;
+    if (n > 0x7FFFFFFFull) return fail(VBF_EINVAL, "too many entries (%llu > 2^31 - 1)", (unsigned long long)n);
+    if (n == 0) return VBF_OK;
+    if (!out_ids) return fail(VBF_EINVAL, "out_ids is NULL");
+    return check_keys(keys, offsets, stride, n);
+}
+
+int offsets_ascend(const uint64_t* offsets, uint64_t n) {
+    if (offsets)
+        for (uint64_t i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i])
+                return fail(VBF_EINVAL, "offsets descend at entry %llu", (unsigned long long)i);
+    return VBF_OK;
+}
+
+// The sort on device pointers, n in [1, 2^31): out_ids[0 .. *n_out) = the distinct keys in
+// ascending order, each by its last put.  One stream synchronisation, for the count and the
+// offsets' check.  *soff_out (optional): the sort's own n + 1 offsets into `keys`, valid until the
+// next sort on the stream.
+// Workspace: 33 bytes per entry (offsets 8, two id buffers 4 + 4, two prefix buffers 8 + 8, the
+// keep flags 1), the levels' geometry (16 bytes per tile) and the select's scratch.
+int memtable_sort(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t* out_ids,
+                  uint64_t* n_out, const uint64_t** soff_out, hipStream_t s) {
+    const uint64_t tile = vbf::memtable_tile();
+    std::vector<uint64_t> bnd;
+    for (uint64_t b = 0; b < n; b += tile) bnd.push_back(b);
+    bnd.push_back(n);
+    const MergeGeometry geo(std::move(bnd));
+    size_t tsel = 0;
+    HIP_TRY(vbf::select_u32(nullptr, &tsel, nullptr, nullptr, nullptr, nullptr, n, s));
+    DevImage w;
+    const auto p_soff = w.add<uint64_t>(n + 1);
+    const auto p_ping = w.add<uint32_t>(n);
+    const auto p_pong = w.add<uint32_t>(n);
+    const auto p_pp = w.add<uint64_t>(n);
+    const auto p_pq = w.add<uint64_t>(n);
+    const auto p_keep = w.add<uint8_t>(n);
+    const auto p_bnd = w.add<uint64_t>(geo.all.size() + 1);
+    const auto p_tl = w.add<uint64_t>(geo.tiles_all.size() + 1);
+    const auto p_split = w.add<uint64_t>(geo.max_tiles);
+    const auto p_misc = w.add<uint64_t>(2);  // [0] the distinct keys, [1] low word: the first descending offset
+    const auto p_tmp = w.add<uint8_t>(tsel);
+    int rc = get_workspace(s, w.bytes, &w.base, kWsMemSort);
+    if (rc) return rc;
+    uint64_t* soff = w.ptr(p_soff);
+    uint64_t* misc = w.ptr(p_misc);
+    if (!geo.all.empty())
+        HIP_TRY(hipMemcpyAsync(w.ptr(p_bnd), geo.all.data(), geo.all.size() * 8, hipMemcpyHostToDevice, s));
+    if (!geo.tiles_all.empty())
+        HIP_TRY(hipMemcpyAsync(w.ptr(p_tl), geo.tiles_all.data(), geo.tiles_all.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(misc, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(misc + 1, 0xFF, 8, s));
+    vbf::CompactArgs a{};
+    a.keys = keys;
+    a.offsets = soff;
+    a.run_off_host_total = n;
+    vbf::phase_begin(vbf::kPhaseMemSort, s);
+    HIP_TRY(vbf::memtable_prefixes(keys, offsets, stride, n, reinterpret_cast<uint32_t*>(misc + 1), soff, w.ptr(p_ping),
+                                   w.ptr(p_pp), s));
+    HIP_TRY(vbf::memtable_tile_sort(a, n, w.ptr(p_ping), w.ptr(p_pp), s));
+    vbf::phase_end(vbf::kPhaseMemSort, s);
+    vbf::phase_begin(vbf::kPhaseMemMerge, s);
+    uint32_t* order = nullptr;
+    uint64_t* opfx = nullptr;
+    HIP_TRY(vbf::merge_levels_from(a, w.ptr(p_bnd), w.ptr(p_tl), geo.nseg_lv.data(), geo.ntiles_lv.data(),
+                                   (uint32_t)geo.nseg_lv.size(), w.ptr(p_ping), w.ptr(p_pong), w.ptr(p_pp), w.ptr(p_pq),
+                                   w.ptr(p_split), &order, &opfx, s));
+    HIP_TRY(vbf::memtable_keep(a, order, opfx, n, w.ptr(p_keep), s));
+    size_t tb = tsel;
+    HIP_TRY(vbf::select_u32(w.ptr(p_tmp), &tb, order, w.ptr(p_keep), out_ids, misc, n, s));
+    vbf::phase_end(vbf::kPhaseMemMerge, s);
+    uint64_t hv[2];
+    HIP_TRY(hipMemcpyAsync(hv, misc, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t bad = (uint32_t)hv[1];
+    if (bad != 0xFFFFFFFFu) return fail(VBF_EINVAL, "offsets descend at entry %u", bad);
+    *n_out = hv[0];
+    if (soff_out) *soff_out = soff;
+    return VBF_OK;
+}
+
+// A batch of host keys as the sort and the filter step take it on the device: the key bytes from
+// the first offset on, and the offsets rebased to that copy.
+struct KeyImage : DevImage {
+    Part<uint8_t> keys;
+    Part<uint64_t> off;
+    uint64_t kb = 0;
+    void lay(const uint64_t* offsets, uint64_t stride, uint64_t n) {
+        kb = offsets ? offsets[n] - offsets[0] : n * stride;
+        keys = add<uint8_t>(kb);
+        off = add<uint64_t>(n + 1, offsets);
+    }
+    int upload(HostCall& c, const uint8_t* k, const uint64_t* offsets, uint64_t n) {
+        int rc = c.up(ptr(keys), kb ? k + (offsets ? offsets[0] : 0) : nullptr, kb);
+        return rc ? rc : c.up_rebased(ptr(off), offsets, n + 1);
+    }
+};
+
+int filter_insert_check(const vbf_filter* f, const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                        uint64_t* n_new) {
+    if (n_new) *n_new = 0;
+    if (!f) return fail(VBF_EINVAL, "filter is NULL");
+    if (n > 0xFFFFFFFEull) return fail(VBF_EINVAL, "too many keys (%llu > 2^32 - 2)", (unsigned long long)n);
+    if (f->bits->m > kInsertMaxBits)
+        return fail(VBF_EINVAL, "filter of %u bits above the insert's cap of 2^30 bits (one u32 of scratch per bit)",
+                    f->bits->m);
+    int rc = check_mk(f->bits->m, f->k, n);
+    return rc ? rc : check_keys(keys, offsets, stride, n);
+}
+
+// mem.rs:209-211 replayed over the batch on a host-resident filter; returns the sets that ran.
+uint64_t host_insert(uint32_t* w, uint32_t m, uint32_t k, const uint8_t* keys, const uint64_t* offsets, uint64_t stride,
+                     uint64_t n, bool lp) {
+    uint64_t fresh = 0;
+    std::vector<uint32_t> idx(k);
+    for (uint64_t j = 0; j < n; ++j) {
+        const uint8_t* kp;
+        uint64_t len;
+        host_key(keys, offsets, stride, j, &kp, &len);
+        const vbf::Prefix p = host_prefix(kp, len, lp);
+        bool contained = true;
+        for (uint32_t i = 0; i < k; ++i) {
+            idx[i] = (uint32_t)(vbf::prefix_hash(p, i) % (uint64_t)m);
+            contained = contained && ((w[idx[i] >> 5] >> (idx[i] & 31)) & 1u);
+        }
+        if (contained) continue;
+        for (uint32_t i = 0; i < k; ++i) w[idx[i] >> 5] |= 1u << (idx[i] & 31);
+        ++fresh;
+    }
+    return fresh;
+}
+
+// The filter step on a device-resident filter and device keys.  Caller holds s.mu (drained), on
+// s.device; n, k > 0.  Counts the keys not contained at their turn, then ORs every key's bits in
+// (the skipped sets would have changed nothing).  One stream synchronisation, for the count.
+int filter_insert_device(Storage& s, vbf_filter* f, const vbf::KeyBatch& kb, uint64_t* fresh, hipStream_t hs) {
+    int rc = storage_wait(s, hs);
+    if (rc) return rc;
+    const uint64_t np = vbf::filter_insert_partials(kb.n);
+    DevImage w;
+    const auto p_first = w.add<uint32_t>(s.m);
+    const auto p_part = w.add<uint32_t>(np);
+    const auto p_cnt = w.add<unsigned long long>(1);
+    if ((rc = get_workspace(hs, w.bytes, &w.base, kWsFilterInsert))) return rc;
+    HIP_TRY(hipMemsetAsync(w.ptr(p_cnt), 0, 8, hs));
+    vbf::phase_begin(vbf::kPhaseFilterInsert, hs);
+    HIP_TRY(vbf::filter_insert_count(kb, s.m, f->k, s.d_words, w.ptr(p_first), w.ptr(p_part), w.ptr(p_cnt), hs));
+    s.mirror_ok = false;
+    s.pristine = false;
+    if ((rc = do_build(kb, s.m, f->k, s.d_words, VBF_BUILD_AUTO, true, hs))) return rc;
+    vbf::phase_end(vbf::kPhaseFilterInsert, hs);
+    if ((rc = storage_mark(s, hs)) || (rc = mirror_after_write(s, hs))) return rc;
+    unsigned long long c = 0;
+    HIP_TRY(hipMemcpyAsync(&c, w.ptr(p_cnt), 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    *fresh = c;
+    return VBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbf_memtable_sort_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t* out_ids,
+                          uint64_t* n_out, void* stream) {
+    int rc = memtable_check(keys, offsets, stride, n, out_ids, n_out);
+    if (rc) return rc;
+    if (n == 0) return ok();
+    FORK_GUARD();
+    rc = memtable_sort(keys, offsets, stride, n, out_ids, n_out, nullptr, (hipStream_t)stream);
+    return rc ? rc : ok();
+}
+
+int vbf_memtable_sort_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t* out_ids,
+                           uint64_t* n_out, int device) {
+    int rc = memtable_check(keys, offsets, stride, n, out_ids, n_out);
+    if (rc) return rc;
+    if (n == 0) return ok();  // no entries: no device needed
+    if ((rc = offsets_ascend(offsets, n))) return rc;
+    HOST_CALL(call, device);
+    KeyImage m;
+    m.lay(offsets, stride, n);
+    const auto p_ids = m.add<uint32_t>(n);
+    if ((rc = m.alloc(call, kWsMemIO)) || (rc = m.upload(call, keys, offsets, n))) return rc;
+    if ((rc = memtable_sort(m.ptr(m.keys), m.ptr(m.off), stride, n, m.ptr(p_ids), n_out, nullptr, call.s))) return rc;
+    if ((rc = call.down(out_ids, m.ptr(p_ids), *n_out))) return rc;
+    return call.finish();
+}
+
+int vbf_filter_insert_dev(vbf_filter* f, const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                          int len_prefix, uint64_t* n_new, void* stream) {
+    int rc = filter_insert_check(f, keys, offsets, stride, n, n_new);
+    if (rc) return rc;
+    Storage& s = *f->bits;
+    std::unique_lock<std::mutex> lk(s.mu);
+    if ((rc = storage_drain(s, lk))) return rc;
+    if (s.host()) return host_resident("vbf_filter_insert_dev");
+    uint64_t fresh = 0;
+    if (n && f->k) {
+        DEVICE_SCOPE(s.device);
+        if ((rc = filter_insert_device(s, f, batch(keys, offsets, 0, stride, n, len_prefix), &fresh,
+                                       (hipStream_t)stream)))
+            return rc;
+    }
+    f->n.fetch_add((uint32_t)fresh);
+    if (n_new) *n_new = fresh;
+    return ok();
+}
+
+int vbf_filter_insert_host(vbf_filter* f, const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                           int len_prefix, uint64_t* n_new) {
+    int rc = filter_insert_check(f, keys, offsets, stride, n, n_new);
+    if (rc) return rc;
+    if ((rc = offsets_ascend(offsets, n))) return rc;
+    Storage& s = *f->bits;
+    std::unique_lock<std::mutex> lk(s.mu);
+    if ((rc = storage_drain(s, lk))) return rc;
+    uint64_t fresh = 0;
+    if (n && f->k) {
+        if (s.host()) {
+            fresh = host_insert(host_words(s), s.m, f->k, keys, offsets, stride, n, len_prefix != 0);
+            if (fresh) s.pristine = false;
+        } else {
+            HOST_CALL(call, s.device);  // after the filter's lock and its drain
+            KeyImage m;
+            m.lay(offsets, stride, n);
+            if ((rc = m.alloc(call, kWsFilterInsertIO)) || (rc = m.upload(call, keys, offsets, n))) return rc;
+            if ((rc = filter_insert_device(s, f, batch(m.ptr(m.keys), m.ptr(m.off), 0, stride, n, len_prefix), &fresh,
+                                           call.s)))
+                return rc;
+            if ((rc = call.finish())) return rc;
+        }
+    }
+    f->n.fetch_add((uint32_t)fresh);
+    if (n_new) *n_new = fresh;
+    return ok();
+}
+
+// One batch of puts through to the SST's files: sort -> gather -> encode (-> the filter step), all
+// on `device` from one upload.
+int vbf_flush_write_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                         const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones,
+                         vbf_filter* filter, uint8_t* data, uint64_t data_cap, uint64_t* data_len, uint8_t* index,
+                         uint64_t index_cap, uint64_t* index_len, uint32_t* out_ids, uint64_t* n_out, int device) {
+    if (!data_len || !index_len || !n_out) return fail(VBF_EINVAL, "data_len / index_len / n_out is NULL");
+    *data_len = *index_len = *n_out = 0;
+    if (n > 0x7FFFFFFFull) return fail(VBF_EINVAL, "too many entries (%llu > 2^31 - 1)", (unsigned long long)n);
+    if (n == 0) return fail(VBF_EINVAL, "Cannot flush an empty table (flusher.rs:40-44, table.rs:262-264)");
+    int rc = check_keys(keys, offsets, stride, n);
+    if (rc || (rc = offsets_ascend(offsets, n))) return rc;
+    if (!offsets && stride > 4079)
+        return fail(VBF_EINVAL, "entry of %llu bytes exceeds a 4096-byte block (BlockIsFull)",
+                    (unsigned long long)(stride + 17));
+    const uint64_t kb = offsets ? offsets[n] - offsets[0] : n * stride;
+    if (!keys && kb) return fail(VBF_EINVAL, "keys is NULL");
+    if (n >= (1ull << 32) / 17 || kb >= (1ull << 32))
+        return fail(VBF_EINVAL, "data.db reaches 2^32 bytes: index.db's u32 block offsets cannot address it");
+    // lock order: the filter's, then the device's
+    std::unique_lock<std::mutex> flk;
+    if (filter) {
+        Storage& fs = *filter->bits;
+        if ((rc = filter_insert_check(filter, keys, offsets, stride, n, nullptr))) return rc;
+        flk = std::unique_lock<std::mutex>(fs.mu);
+        if ((rc = storage_drain(fs, flk))) return rc;
+        if (fs.host())
+            return fail(VBF_EINVAL, "vbf_flush_write_host: the filter is host-resident (VBF_DEVICE_HOST); a memtable's "
+                                    "own host filter stays with its caller (pass NULL)");
+        if (fs.device != device)
+            return fail(VBF_EINVAL, "the filter lives on device %d, the flush runs on device %d", fs.device, device);
+    }
+    HOST_CALL(call, device);
+    KeyImage m;  // keys | offsets | val | created | tombstones | ids
+    m.lay(offsets, stride, n);
+    const auto p_val = m.add<uint32_t>(n, val_offsets);
+    const auto p_cr = m.add<int64_t>(n, created_ms);
+    const auto p_tb = m.add<uint8_t>(n, tombstones);
+    const auto p_ids = m.add<uint32_t>(n);
+    if ((rc = m.alloc(call, kWsMemIO)) || (rc = m.upload(call, keys, offsets, n)) ||
+        (rc = call.up(m.ptr(p_val), val_offsets, n)) || (rc = call.up(m.ptr(p_cr), created_ms, n)) ||
+        (rc = call.up(m.ptr(p_tb), tombstones, n)))
+        return rc;
+    uint64_t nd = 0;
+    const uint64_t* soff = nullptr;
+    if ((rc = memtable_sort(m.ptr(m.keys), m.ptr(m.off), stride, n, m.ptr(p_ids), &nd, &soff, call.s))) return rc;
+    // the table in key order in the encoder's layout, then its files; capacities that always suffice
+    DevImage q;  // keys | offsets | created | tombstones | val | data.db | index.db
+    const auto q_keys = q.add<uint8_t>(kb);
+    const auto q_off = q.add<uint64_t>(nd + 1);
+    const auto q_cr = q.add<int64_t>(nd, created_ms);
+    const auto q_tb = q.add<uint8_t>(nd, tombstones);
+    const auto q_val = q.add<uint32_t>(nd, val_offsets);
+    const auto q_data = q.add<uint8_t>(kb + 17 * nd, data);
+    const auto q_idx = q.add<uint8_t>(kb + 8 * nd, index);
+    if ((rc = q.alloc(call, kWsMemOut))) return rc;
+    uint64_t gkb = 0, nb = 0;
+    if ((rc = gather_entries(m.ptr(m.keys), soff, m.ptr(p_cr), m.ptr(p_tb), m.ptr(p_val), m.ptr(p_ids), nd,
+                             q.ptr(q_keys), kb, q.ptr(q_off), q.ptr(q_cr), q.ptr(q_tb), q.ptr(q_val), &gkb, call.s)))
+        return rc;
+    if ((rc = sst_encode(q.ptr(q_keys), q.ptr(q_off), 0, nd, q.ptr(q_val), q.ptr(q_cr), q.ptr(q_tb), q.ptr(q_data),
+                         kb + 17 * nd, data_len, q.ptr(q_idx), kb + 8 * nd, index_len, nullptr, 0, &nb, call.s)))
+        return rc;
+    *n_out = nd;
+    if (data && data_cap < *data_len)
+        return fail(VBF_EINVAL, "data holds %llu < %llu bytes", (unsigned long long)data_cap,
+                    (unsigned long long)*data_len);
+    if (index && index_cap < *index_len)
+        return fail(VBF_EINVAL, "index holds %llu < %llu bytes", (unsigned long long)index_cap,
+                    (unsigned long long)*index_len);
+    // MemTable::insert's filter step over every put, in arrival order (mem.rs:209-211)
+    if (filter && filter->k) {
+        uint64_t fresh = 0;
+        if ((rc = filter_insert_device(*filter->bits, filter, batch(m.ptr(m.keys), m.ptr(m.off), 0, stride, n, 1), &fresh,
+                                       call.s)))
+            return rc;
+        filter->n.fetch_add((uint32_t)fresh);
+    }
+    if ((rc = call.down(data, q.ptr(q_data), *data_len)) || (rc = call.down(index, q.ptr(q_idx), *index_len)) ||
+        (rc = call.down(out_ids, m.ptr(p_ids), nd)))
+        return rc;
+    return call.finish();
 }
 
 }  // extern "C"

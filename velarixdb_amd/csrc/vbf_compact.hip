@@ -23,46 +23,12 @@
 #include <hipcub/device/device_scan.hpp>
 #include <hipcub/device/device_select.hpp>
 
+#include "vbf_keycmp.hpp"
 #include "vbf_kernels.hpp"
 
 namespace vbf {
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-// Rust `Ord for [u8]` on two keys of the arena: 8 bytes at a time as big-endian words (global
-// memory takes unaligned 8-byte loads), then the tail byte by byte.
-__device__ __forceinline__ uint64_t ld_be64(const uint8_t* p) {
-    uint64_t w;
-    __builtin_memcpy(&w, p, 8);
-    return __builtin_bswap64(w);
-}
-
-__device__ __forceinline__ int cmp_keys(const uint8_t* ka, uint64_t la, const uint8_t* kb, uint64_t lb) {
-    const uint64_t n = la < lb ? la : lb;
-    uint64_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-        const uint64_t x = ld_be64(ka + i), y = ld_be64(kb + i);
-        if (x != y) return x < y ? -1 : 1;
-    }
-    for (; i < n; ++i) {
-        const uint32_t x = ka[i], y = kb[i];
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return la < lb ? -1 : (la > lb ? 1 : 0);
-}
-
-__device__ __forceinline__ int cmp_ids(const CompactArgs& a, uint32_t x, uint32_t y) {
-    const uint64_t bx = a.offsets[x], by = a.offsets[y];
-    return cmp_keys(a.keys + bx, a.offsets[x + 1] - bx, a.keys + by, a.offsets[y + 1] - by);
-}
-
-// Big-endian 8-byte prefix of a key (zero-padded): prefixes order keys except on ties.
-__device__ __forceinline__ uint64_t key_prefix8(const uint8_t* k, uint64_t len) {
-    if (len >= 8) return ld_be64(k);
-    uint64_t w = 0;
-    for (uint64_t i = 0; i < len; ++i) w |= (uint64_t)k[i] << (56 - 8 * i);
-    return w;
-}
 
 __global__ __launch_bounds__(256) void k_prefixes(CompactArgs a, uint32_t* ids, uint64_t* pfx) {
     const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -70,12 +36,6 @@ __global__ __launch_bounds__(256) void k_prefixes(CompactArgs a, uint32_t* ids, 
     const uint64_t b = a.offsets[e];
     ids[e] = (uint32_t)e;
     pfx[e] = key_prefix8(a.keys + b, a.offsets[e + 1] - b);
-}
-
-// (prefix, id) order: prefixes first, the full keys only on a prefix tie.
-__device__ __forceinline__ int cmp_pid(const CompactArgs& a, uint64_t px, uint32_t x, uint64_t py, uint32_t y) {
-    if (px != py) return px < py ? -1 : 1;
-    return cmp_ids(a, x, y);
 }
 
 // Merge levels, two-level merge path.  Pairs (2p, 2p+1) of segments [bnd[s], bnd[s+1]) are cut
@@ -309,8 +269,20 @@ hipError_t compact_merge_levels(const CompactArgs& a, const uint64_t* d_bnd_all,
                                 uint32_t** result, uint64_t** presult, hipStream_t s) {
     const uint64_t total = a.run_off_host_total;
     hipLaunchKernelGGL(k_prefixes, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, a, ping, pping);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return merge_levels_from(a, d_bnd_all, d_tiles_all, nseg_per_level, ntiles_per_level, nlevels, ping, pong, pping,
+                             ppong, split, result, presult, s);
+}
+
+// The levels alone, from ping buffers that already hold (id, prefix) pairs sorted within every
+// first-level segment: the compaction merge after k_prefixes (its runs are sorted tables), the
+// memtable sort after its tile sort.
+hipError_t merge_levels_from(const CompactArgs& a, const uint64_t* d_bnd_all, const uint64_t* d_tiles_all,
+                             const uint32_t* nseg_per_level, const uint64_t* ntiles_per_level, uint32_t nlevels,
+                             uint32_t* ping, uint32_t* pong, uint64_t* pping, uint64_t* ppong, uint64_t* split,
+                             uint32_t** result, uint64_t** presult, hipStream_t s) {
+    hipError_t e = hipSuccess;
     uint32_t* in = ping;
     uint32_t* out = pong;
     uint64_t* pin = pping;

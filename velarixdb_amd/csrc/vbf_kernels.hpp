@@ -33,7 +33,8 @@ enum Phase { kPhaseTileSort = 0, kPhaseTranspose = 1, kPhaseSegOr = 2, kPhaseAto
              kPhaseProbeSeg = 12, kPhaseProbeOut = 13, kPhaseEncTile = 14, kPhaseEncScan = 15,
              kPhaseEncIndex = 16, kPhaseEncData = 17, kPhaseTableOpen = 18, kPhaseTableGet = 19,
              kPhaseScanRank = 20, kPhaseScanEmit = 21, kPhaseVlogSizes = 22, kPhaseVlogCopy = 23,
-             kPhaseVlogEncode = 24, kNumPhases = 25 };
+             kPhaseVlogEncode = 24, kPhaseMemSort = 25, kPhaseMemMerge = 26, kPhaseFilterInsert = 27,
+             kNumPhases = 28 };
 void phase_begin(int phase, hipStream_t s);
 void phase_end(int phase, hipStream_t s);
 
@@ -327,6 +328,10 @@ hipError_t compact_merge_levels(const CompactArgs& a, const uint64_t* d_bnd_all,
                                 const uint32_t* nseg_per_level, const uint64_t* ntiles_per_level, uint32_t nlevels,
                                 uint32_t* ping, uint32_t* pong, uint64_t* pping, uint64_t* ppong, uint64_t* split,
                                 uint32_t** result, uint64_t** presult, hipStream_t s);
+hipError_t merge_levels_from(const CompactArgs& a, const uint64_t* d_bnd_all, const uint64_t* d_tiles_all,
+                             const uint32_t* nseg_per_level, const uint64_t* ntiles_per_level, uint32_t nlevels,
+                             uint32_t* ping, uint32_t* pong, uint64_t* pping, uint64_t* ppong, uint64_t* split,
+                             uint32_t** result, uint64_t** presult, hipStream_t s);
 uint32_t compact_tile();
 hipError_t compact_fold(const CompactArgs& a, const uint32_t* order, const uint64_t* opfx, uint64_t total,
                         uint8_t* keep, uint32_t* sel, uint8_t* upd, int64_t* upd_time, hipStream_t s);
@@ -337,6 +342,20 @@ hipError_t select_i64(void* tmp, size_t* bytes, const int64_t* in, const uint8_t
 hipError_t gather_lens(const uint64_t* offsets, const uint32_t* ids, uint64_t n, uint64_t* lens, hipStream_t s);
 hipError_t scan_u64(void* tmp, size_t* bytes, const uint64_t* in, uint64_t* out, uint64_t n, hipStream_t s);
 hipError_t gather(const GatherArgs& g, hipStream_t s);
+// Memtable flush (vbf_memtable.hip).  The sort works on `soff`, its own copy of the offsets (n + 1;
+// generated from the stride without offsets, every key empty when *err reports descending offsets),
+// which CompactArgs::offsets then names for the tile sort, the merge levels and the keep pass.
+uint32_t memtable_tile();  // == compact_tile()
+hipError_t memtable_prefixes(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, uint32_t* err,
+                             uint64_t* soff, uint32_t* ids, uint64_t* pfx, hipStream_t s);
+hipError_t memtable_tile_sort(const CompactArgs& a, uint64_t n, uint32_t* ids, uint64_t* pfx, hipStream_t s);
+hipError_t memtable_keep(const CompactArgs& a, const uint32_t* order, const uint64_t* opfx, uint64_t n, uint8_t* keep,
+                         hipStream_t s);
+// The memtable's `if !contains(key) { set(key) }` count: `first` holds m u32, `partial`
+// filter_insert_partials(n) u32; the keys not contained at their turn are added to *count.
+uint64_t filter_insert_partials(uint64_t n);
+hipError_t filter_insert_count(const KeyBatch& kb, uint32_t m, uint32_t k, const uint32_t* words, uint32_t* first,
+                               uint32_t* partial, unsigned long long* count, hipStream_t s);
 hipError_t gen_sst_fixed(uint64_t seed, uint64_t base, uint64_t n, uint32_t len, uint8_t* data, uint32_t* blocks,
                          hipStream_t s);
 }  // namespace vbf

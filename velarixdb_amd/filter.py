@@ -260,6 +260,19 @@ class BloomFilter:
     def set_many(self, keys):
         self.set_batch(keys if isinstance(keys, HostBatch) else pack(keys))
 
+    def insert_many(self, keys):
+        """MemTable::insert's `if !contains(key) { set(key) }` (memtable/mem.rs:209-211) over the
+        keys in order (vbf_filter_insert_host) -> the number of keys that were not contained when
+        their turn came, which is what no_of_elements grew by."""
+        b = keys if isinstance(keys, HostBatch) else pack(keys)
+        d, o = b.ptrs()
+        n_new = ctypes.c_uint64()
+        try:
+            call("vbf_filter_insert_host", self._h, d, o, b.stride, b.n, b.len_prefix, ctypes.byref(n_new))
+        except VbfError as e:
+            _raise("insert", e)
+        return n_new.value
+
     def set_many_async(self, keys, zero_copy=False):
         """set_many that returns before the GPU work is done (vbf_filter_set_host_async).  Later
         calls on the filter wait for it; sync() waits.  By default the library copies the keys
