@@ -42,6 +42,8 @@
  *   DataStore::get_value_from_vlog     src/db/store.rs:628-641     -> vbf_vlog_get_* (tombstone -> no value)
  *   ValueLog::append                   src/vlog/v_log.rs:173-196   -> vbf_vlog_encode_* (val_offsets)
  *   ValueLogEntry::serialize           src/vlog/v_log.rs:291-309   -> vbf_vlog_encode_* (the bytes)
+ *   ValueLog::recover                  src/fs/mod.rs:520-577       -> vbf_vlog_walk_* (budget UINT64_MAX)
+ *   read_chunk_to_garbage_collect      src/fs/mod.rs:579-651       -> vbf_vlog_walk_* (budget = bytes)
  *   MemTable::insert (the SkipMap)     src/memtable/mem.rs:207-221 -> vbf_memtable_sort_* (last put wins)
  *   MemTable::insert (contains, set)   src/memtable/mem.rs:209-211 -> vbf_filter_insert_host / _dev
  *   Flusher::flush                     src/flush/flusher.rs:37-64  -> vbf_flush_write_host
@@ -67,7 +69,7 @@
  * shares its staging: vbf_build_host, vbf_probe_host and the filters' set_host / contains_host /
  * words copies take turns on the device's two staging streams, and the other `_host` entry points
  * (sst_decode, sst_encode, rebuild_from_sst, multi_probe, compact_merge, compact_write,
- * table_open, table_get, table_scan, vlog_open, vlog_get, vlog_encode, memtable_sort,
+ * table_open, table_get, table_scan, vlog_open, vlog_get, vlog_encode, vlog_walk, memtable_sort,
  * flush_write, and filter_insert_host on a device-resident filter) take turns on its shared
  * stream, each from its first upload to its last download; the two groups overlap each other, and
  * devices never wait for each other.  A call that spans several devices (vbf_multi_probe_host over filters on several GPUs)
@@ -767,8 +769,8 @@ int vbf_table_scan_host(const uint8_t* bounds, const uint64_t* bounds_off, uint6
  * key (the reference's load_buffer! treats a 0-byte read as UnexpectedEof, so its get of either
  * fails); an entry whose header or body runs past the end of the log is reported as bad, per item
  * (the reference's single read would return a short buffer there; no short value is returned here).
- * Out of scope: ValueLog::recover and the GC's chunk read (a serial walk of an unindexed file), hole
- * punching, file I/O.
+ * ValueLog::recover and the GC's chunk read, the serial walks of the unindexed file, are
+ * vbf_vlog_walk_* below.  Out of scope: hole punching, file I/O.
  *
  * A vbf_vlog is a window of the log on a device: bytes[0..len) are the file's bytes
  * [base, base + len).  `base` is the log's tail: the GC punches the front of the file away, so a
@@ -845,6 +847,67 @@ int vbf_vlog_encode_host(const uint8_t* keys, const uint64_t* offsets, uint64_t 
                          const uint8_t* values, const uint64_t* value_off,
                          const int64_t* created_ms, const uint8_t* tombstones, uint64_t base,
                          uint8_t* out, uint64_t out_cap, uint64_t* out_len, uint32_t* val_offsets, int device);
+
+/* ---- the walk of the value log: crash recovery and the GC's chunk read ----
+ * ValueLog::recover(head) is VLogFileNode::recover (fs/mod.rs:520-577): seek to the head offset
+ * (:524) and read entry after entry -- the four header fields (:529-556), the key (:557-558), the
+ * value (:563-564) -- until a read returns 0 bytes at an entry's first field (:531-533).
+ * recover_memtable (db/recovery.rs:245-286) turns the entries into memtable inserts; the first one
+ * is already in an SST and is skipped (recovery.rs:261-264).  read_chunk_to_garbage_collect(bytes,
+ * tail) (fs/mod.rs:579-651) is the same loop from the tail (:587) that also adds up the bytes read
+ * (:594-633) and returns after the entry that brought them to `bytes` or more (:646-649);
+ * GC::gc_handler (gc/garbage_collector.rs:168-262) looks every key up and re-appends the live ones.
+ *
+ * The walk runs over an open vbf_vlog, from file position `start`, following
+ * p -> p + 17 + key_len(p) + val_len(p).  It stops with *stop = */
+#define VBF_WALK_END 0     /* the chain reached base + len exactly (fs/mod.rs:531-533, :595-597)      */
+#define VBF_WALK_BUDGET 1  /* after the entry that brought the bytes read to >= budget (:646-649)     */
+#define VBF_WALK_TORN 2    /* the entry at *end_off has a header or a body that crosses base + len    */
+/* Budget: the test `bytes read >= budget` runs after each whole entry (fs/mod.rs:646-649), so
+ * budget = 0 yields exactly one entry when one exists, and it wins over END when the same entry
+ * also ends the log; budget = UINT64_MAX is recover.  Bytes read = *end_off - start.
+ * Start: start == base + len is VBF_OK with no entry and VBF_WALK_END; start outside
+ * [base, base + len] is VBF_EINVAL.  `start` must be an entry's first byte, as the reference's
+ * head and tail offsets are: the walk has no way to tell.
+ * Torn tail, this library's reading: a log cut by a crash ends in a partial entry.  That is its
+ * normal state, not an error: the entries before it are returned, *end_off is the torn entry's
+ * position and *stop = VBF_WALK_TORN (the reference's short read would return an entry of garbage
+ * there, :558-575; as with vbf_vlog_get_*, no short entry is returned here).  Hops are computed in
+ * 64 bits: key_len = val_len = 0xFFFFFFFF is torn and never wraps.
+ * Fields: tombstones[i] is 1 iff the byte is 1 (:556); created_ms[i] is the stored 8 bytes (:549);
+ * zero-length keys and values are ordinary entries, as above.  Entry i lies at entry_off[i], its
+ * key is keys[key_off[i] .. key_off[i+1]), its value values[value_off[i] .. value_off[i+1]) -- the
+ * entry's own value, tombstone or not.  entry_off, key_off and value_off have n + 1 entries;
+ * entry_off[n] = *end_off, key_off and value_off start at 0.  val_offsets[i] is entry_off[i] as u32,
+ * what vbf_sst_encode_*, vbf_flush_write_host and vbf_vlog_get_* take; val_offsets given while an
+ * entry lies at or beyond 2^32 is VBF_EINVAL.
+ * Outputs: every array may be NULL; all of them NULL is the size query; the five scalars (*n_out,
+ * *key_bytes, *value_bytes, *end_off, *stop) are always written.  A capacity that is too small
+ * (entries_cap < n with any per-entry array given -- the n + 1 arrays need entries_cap + 1
+ * elements --, keys_cap, values_cap) is VBF_EINVAL with the sizes written and no array touched.  At
+ * most 2^31 - 2 entries.  Every argument check (NULL scalars, NULL handle, start outside the window)
+ * runs on the host before any HIP call.  _dev runs on the current device, which must be the
+ * handle's (VBF_EINVAL otherwise).
+ * Cost: the window is walked in segments of 8 MiB, in order, and the walk ends with the segment in
+ * which the budget is met or the chain stops: a GC chunk costs its own bytes, not the window's.  No
+ * lane follows the chain entry by entry: per segment the dependent steps of any lane are bounded by
+ * the segment's groups (64) + the tiles of a group (32) + the entries of a tile (241); see
+ * csrc/vbf_vlog_walk.hip.  _dev synchronises `stream` once per segment (the segment's sizes and
+ * where the chain left it); the emit and copy passes stay queued.  With outputs and more than one
+ * segment the segments' passes run a second time, without synchronising.  Workspace (cached per
+ * stream like every other): about 4.4 bytes per byte of the largest segment walked plus 32 bytes
+ * per possible entry of it (242 per tile), 51 MiB for a full segment, whatever the window's length.  _host: every
+ * array in host memory, synchronous, on the handle's device. */
+int vbf_vlog_walk_dev(const vbf_vlog* v, uint64_t start, uint64_t budget, uint64_t* entry_off,
+                      uint32_t* val_offsets, uint8_t* keys, uint64_t keys_cap, uint64_t* key_off, uint8_t* values,
+                      uint64_t values_cap, uint64_t* value_off, int64_t* created_ms, uint8_t* tombstones,
+                      uint64_t entries_cap, uint64_t* n_out, uint64_t* key_bytes, uint64_t* value_bytes,
+                      uint64_t* end_off, int* stop, void* stream);
+int vbf_vlog_walk_host(const vbf_vlog* v, uint64_t start, uint64_t budget, uint64_t* entry_off,
+                       uint32_t* val_offsets, uint8_t* keys, uint64_t keys_cap, uint64_t* key_off, uint8_t* values,
+                       uint64_t values_cap, uint64_t* value_off, int64_t* created_ms, uint8_t* tombstones,
+                       uint64_t entries_cap, uint64_t* n_out, uint64_t* key_bytes, uint64_t* value_bytes,
+                       uint64_t* end_off, int* stop);
 
 #ifdef __cplusplus
 }

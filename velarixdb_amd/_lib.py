@@ -29,6 +29,7 @@ VBF_SCAN_KEEP_TOMBSTONES, VBF_SCAN_END_EXCLUSIVE = 1, 2  # vbf_table_scan_* flag
 # vbf_vlog_get_* status
 (VBF_VLOG_SKIPPED, VBF_VLOG_VALUE, VBF_VLOG_TOMBSTONE, VBF_VLOG_NONE, VBF_VLOG_BAD,
  VBF_VLOG_KEY_MISMATCH) = range(6)
+VBF_WALK_END, VBF_WALK_BUDGET, VBF_WALK_TORN = 0, 1, 2  # vbf_vlog_walk_* stop
 
 _u8p = ctypes.c_void_p  # raw pointers (host or device) travel as integers
 _u64 = ctypes.c_uint64
@@ -148,6 +149,12 @@ SIGNATURES = {
                                     _vp, _vp]),
     "vbf_vlog_encode_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64),
                                      _vp, _int]),
+    "vbf_vlog_walk_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64,
+                                  ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                  ctypes.POINTER(_u64), ctypes.POINTER(_int), _vp]),
+    "vbf_vlog_walk_host": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64,
+                                   ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                   ctypes.POINTER(_u64), ctypes.POINTER(_int)]),
     "vbf_memtable_sort_dev": (_int, [_vp, _vp, _u64, _u64, _vp, ctypes.POINTER(_u64), _vp]),
     "vbf_memtable_sort_host": (_int, [_vp, _vp, _u64, _u64, _vp, ctypes.POINTER(_u64), _int]),
     "vbf_filter_insert_host": (_int, [_vp, _vp, _vp, _u64, _u64, _int, ctypes.POINTER(_u64)]),

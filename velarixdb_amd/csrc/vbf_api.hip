@@ -179,6 +179,8 @@ enum WsSlot {
     kWsMemOut = 28,
     kWsFilterInsert = 29,
     kWsFilterInsertIO = 30,
+    kWsVlogWalk = 31,
+    kWsVlogWalkOut = 32,
 };
 struct Workspace {
     int device;
@@ -4604,6 +4606,295 @@ int vbf_vlog_encode_host(const uint8_t* keys, const uint64_t* offsets, uint64_t 
     if ((rc = vlog_enc_emit(a, call.s))) return rc;
     if ((rc = call.down(out, a.out, a.total)) || (rc = call.down(val_offsets, a.val_offsets, n))) return rc;
     return call.finish();
+}
+
+}  // extern "C"
+
+// ---- the walk of the value log (ValueLog::recover, read_chunk_to_garbage_collect) ----
+
+namespace {
+
+// What the first sweep leaves for the second: per segment its entry position and sizes.
+struct WalkSegment {
+    uint64_t pos, n, kb, vb;
+};
+struct WalkPlan {
+    vbf::WalkArgs a{};       // the workspace's parts; seg0 / ntiles / q0 / cap of the last segment walked
+    void* scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+    uint64_t s_rel = 0, lim = 0, t_end = 0;  // start, inclusion limit, the end of the tiles walked
+    std::vector<WalkSegment> segs;
+    uint64_t n = 0, kb = 0, vb = 0, end_rel = 0, last_entry = 0;
+    int stop = VBF_WALK_END;
+};
+
+// The argument checks of vbf_vlog_walk_* that need no HIP call; the five scalars are written.
+int walk_check(const vbf_vlog* v, uint64_t start, uint64_t* n_out, uint64_t* key_bytes, uint64_t* value_bytes,
+               uint64_t* end_off, int* stop) {
+    if (!n_out) return fail(VBF_EINVAL, "n_out is NULL");
+    if (!key_bytes) return fail(VBF_EINVAL, "key_bytes is NULL");
+    if (!value_bytes) return fail(VBF_EINVAL, "value_bytes is NULL");
+    if (!end_off) return fail(VBF_EINVAL, "end_off is NULL");
+    if (!stop) return fail(VBF_EINVAL, "stop is NULL");
+    *n_out = *key_bytes = *value_bytes = 0;
+    *end_off = start;
+    *stop = VBF_WALK_END;
+    if (!v) return fail(VBF_EINVAL, "vlog is NULL");
+    if (start < v->base || start - v->base > v->len)
+        return fail(VBF_EINVAL, "start %llu outside the window [%llu, %llu]", (unsigned long long)start,
+                    (unsigned long long)v->base, (unsigned long long)(v->base + v->len));
+    return VBF_OK;
+}
+
+// One segment's arguments: it starts at the tile of `pos` and covers at most kWalkSegment bytes.
+void walk_segment_args(WalkPlan* p, uint64_t pos) {
+    vbf::WalkArgs& a = p->a;
+    a.seg0 = pos / vbf::kWalkTile * vbf::kWalkTile;
+    const uint64_t seg_end = std::min<uint64_t>(a.seg0 + vbf::kWalkSegment, p->t_end);
+    a.ntiles = (uint32_t)((seg_end - a.seg0) / vbf::kWalkTile);
+    a.q0 = (uint32_t)(pos - a.seg0);
+    a.cap = std::min(std::min(seg_end, a.len), p->lim);
+}
+
+// The first sweep, on the log's device: every segment from `start` until the budget is met or the
+// chain stops, one stream synchronisation per segment (its result).  Workspace (slot kWsVlogWalk):
+// about 4.4 bytes per byte of the largest segment walked (at most kWalkSegment) plus 32 bytes per
+// possible entry of it.
+int walk_sweep(const vbf_vlog* v, uint64_t start, uint64_t budget, hipStream_t s, WalkPlan* p) {
+    const uint64_t len = v->len, T = vbf::kWalkTile;
+    p->s_rel = start - v->base;
+    // entries are included while they start below lim: the first always, the others while the bytes
+    // read before them are below the budget
+    const uint64_t limit = p->s_rel + budget < budget ? ~0ull : p->s_rel + budget;
+    p->lim = std::max(limit, p->s_rel + 1);
+    p->t_end = (std::min(len, p->lim) + T - 1) / T * T;
+    const uint64_t span = p->t_end - p->s_rel / T * T;
+    const uint64_t nt = std::min<uint64_t>(span, vbf::kWalkSegment) / T, ng = (nt + vbf::kWalkGroup - 1) / vbf::kWalkGroup;
+    const uint64_t slots = nt * (T / 17 + 1) + 1;
+    HIP_TRY(vbf::scan_u64(nullptr, &p->scan_bytes, nullptr, nullptr, nt + 1, s));
+    uint64_t off = 0;
+    auto part = [&off](uint64_t bytes) {
+        const uint64_t o = off;
+        off += align256(bytes);
+        return o;
+    };
+    const uint64_t o_exit = part(nt * T * 4), o_gexit = part(ng * T * 4), o_tentry = part(nt * 4);
+    const uint64_t o_pos = part(nt * vbf::kWalkSlots * 2), o_kpre = part(nt * vbf::kWalkSlots * 2);
+    const uint64_t o_cnt = part((nt + 1) * 8), o_ksum = part((nt + 1) * 8), o_vsum = part((nt + 1) * 8);
+    const uint64_t o_tend = part(nt * 8), o_ttorn = part(nt * 4);
+    const uint64_t o_cbase = part((nt + 1) * 8), o_kbase = part((nt + 1) * 8), o_vbase = part((nt + 1) * 8);
+    const uint64_t o_ko = part(slots * 8), o_ks = part(slots * 8), o_vo = part(slots * 8), o_vs = part(slots * 8);
+    const uint64_t o_res = part(sizeof(vbf::WalkRes)), o_tmp = part(p->scan_bytes);
+    void* ws = nullptr;
+    int rc = get_workspace(s, off, &ws, kWsVlogWalk);
+    if (rc) return rc;
+    char* b = static_cast<char*>(ws);
+    vbf::WalkArgs& a = p->a;
+    a.bytes = v->bytes;
+    a.len = len;
+    a.base = v->base;
+    a.lim = p->lim;
+    a.exit = reinterpret_cast<uint32_t*>(b + o_exit);
+    a.gexit = reinterpret_cast<uint32_t*>(b + o_gexit);
+    a.tentry = reinterpret_cast<uint32_t*>(b + o_tentry);
+    a.pos = reinterpret_cast<uint16_t*>(b + o_pos);
+    a.kpre = reinterpret_cast<uint16_t*>(b + o_kpre);
+    a.cnt = reinterpret_cast<uint64_t*>(b + o_cnt);
+    a.ksum = reinterpret_cast<uint64_t*>(b + o_ksum);
+    a.vsum = reinterpret_cast<uint64_t*>(b + o_vsum);
+    a.tend = reinterpret_cast<uint64_t*>(b + o_tend);
+    a.ttorn = reinterpret_cast<uint32_t*>(b + o_ttorn);
+    a.cbase = reinterpret_cast<uint64_t*>(b + o_cbase);
+    a.kbase = reinterpret_cast<uint64_t*>(b + o_kbase);
+    a.vbase = reinterpret_cast<uint64_t*>(b + o_vbase);
+    a.ko = reinterpret_cast<uint64_t*>(b + o_ko);
+    a.ks = reinterpret_cast<uint64_t*>(b + o_ks);
+    a.vo = reinterpret_cast<uint64_t*>(b + o_vo);
+    a.vs = reinterpret_cast<uint64_t*>(b + o_vs);
+    a.res = reinterpret_cast<vbf::WalkRes*>(b + o_res);
+    p->scan_tmp = b + o_tmp;
+    uint64_t pos = p->s_rel;
+    for (;;) {
+        walk_segment_args(p, pos);
+        vbf::WalkRes r{};
+        HIP_TRY(vbf::walk_passes(a, p->scan_tmp, p->scan_bytes, s));
+        HIP_TRY(hipMemcpyAsync(&r, a.res, sizeof(r), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        p->segs.push_back(WalkSegment{pos, r.n, r.kbytes, r.vbytes});
+        p->n += r.n;
+        p->kb += r.kbytes;
+        p->vb += r.vbytes;
+        if (r.n) p->last_entry = r.last_entry;
+        p->end_rel = r.end;
+        if (r.end < pos || r.end > len || (r.end == pos && !r.torn))  // never: the walk only moves forward
+            return fail(VBF_EHIP, "the walk of the segment at %llu ended at %llu", (unsigned long long)pos,
+                        (unsigned long long)r.end);
+        if (r.torn) {
+            p->stop = VBF_WALK_TORN;
+        } else if (r.end >= limit) {  // the reference tests the budget after each whole entry, before the next read
+            p->stop = VBF_WALK_BUDGET;
+        } else if (r.end == len) {
+            p->stop = VBF_WALK_END;
+        } else {
+            pos = r.end;
+            continue;
+        }
+        return VBF_OK;
+    }
+}
+
+// The sizes, the limits and the capacity rule; the scalars are written before any verdict.
+int walk_sizes(const vbf_vlog* v, const WalkPlan& p, const vbf::WalkOut& o, uint64_t keys_cap, uint64_t values_cap,
+               uint64_t entries_cap, uint64_t* n_out, uint64_t* key_bytes, uint64_t* value_bytes, uint64_t* end_off,
+               int* stop) {
+    *n_out = p.n;
+    *key_bytes = p.kb;
+    *value_bytes = p.vb;
+    *end_off = v->base + p.end_rel;
+    *stop = p.stop;
+    if (p.n > 0x7FFFFFFEull)
+        return fail(VBF_EINVAL, "too many entries: %llu (limit 2^31 - 2)", (unsigned long long)p.n);
+    if (o.val_offsets && p.n && v->base + p.last_entry >= kVlogMaxOffset)
+        return fail(VBF_EINVAL, "the entry at %llu lies at or beyond 2^32: a u32 val_offset cannot address it",
+                    (unsigned long long)(v->base + p.last_entry));
+    const bool per_entry = o.entry_off || o.val_offsets || o.key_off || o.value_off || o.created || o.tomb;
+    if (per_entry && entries_cap < p.n)
+        return fail(VBF_EINVAL, "entries_cap %llu < %llu entries", (unsigned long long)entries_cap, (unsigned long long)p.n);
+    if (o.keys && keys_cap < p.kb)
+        return fail(VBF_EINVAL, "keys_cap %llu < %llu key bytes", (unsigned long long)keys_cap, (unsigned long long)p.kb);
+    if (o.values && values_cap < p.vb)
+        return fail(VBF_EINVAL, "values_cap %llu < %llu value bytes", (unsigned long long)values_cap,
+                    (unsigned long long)p.vb);
+    return VBF_OK;
+}
+
+inline bool walk_any(const vbf::WalkOut& o) {
+    return o.entry_off || o.val_offsets || o.keys || o.key_off || o.values || o.value_off || o.created || o.tomb;
+}
+
+// The second sweep, queued on s: the outputs of every segment.  The workspace still holds the last
+// segment walked; with more than one segment the passes run again per segment (no synchronisation:
+// the host knows every entry position and size).
+int walk_fill(WalkPlan* p, vbf::WalkOut o, hipStream_t s) {
+    const size_t ns = p->segs.size();
+    for (size_t k = 0; k < ns; ++k) {
+        const WalkSegment& g = p->segs[k];
+        if (ns > 1) {
+            walk_segment_args(p, g.pos);
+            HIP_TRY(vbf::walk_passes(p->a, p->scan_tmp, p->scan_bytes, s));
+        }
+        o.n_seg = g.n;
+        o.kb_seg = g.kb;
+        o.vb_seg = g.vb;
+        HIP_TRY(vbf::walk_emit(p->a, o, s));
+        o.j0 += g.n;
+        o.k0 += g.kb;
+        o.v0 += g.vb;
+    }
+    HIP_TRY(vbf::walk_tail(o, p->n, p->a.base + p->end_rel, p->kb, p->vb, s));
+    return VBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbf_vlog_walk_dev(const vbf_vlog* v, uint64_t start, uint64_t budget, uint64_t* entry_off, uint32_t* val_offsets,
+                      uint8_t* keys, uint64_t keys_cap, uint64_t* key_off, uint8_t* values, uint64_t values_cap,
+                      uint64_t* value_off, int64_t* created_ms, uint8_t* tombstones, uint64_t entries_cap,
+                      uint64_t* n_out, uint64_t* key_bytes, uint64_t* value_bytes, uint64_t* end_off, int* stop,
+                      void* stream) {
+    int rc = walk_check(v, start, n_out, key_bytes, value_bytes, end_off, stop);
+    if (rc) return rc;
+    vbf::WalkOut o{};
+    o.entry_off = entry_off;
+    o.val_offsets = val_offsets;
+    o.keys = keys;
+    o.key_off = key_off;
+    o.values = values;
+    o.value_off = value_off;
+    o.created = created_ms;
+    o.tomb = tombstones;
+    const bool empty = start - v->base == v->len;
+    if (empty && !walk_any(o)) return ok();
+    FORK_GUARD();
+    hipStream_t s = (hipStream_t)stream;
+    int cur = -1;
+    HIP_TRY(hipGetDevice(&cur));
+    if (cur != v->device)
+        return fail(VBF_EINVAL, "the log lives on device %d, the current device is %d", v->device, cur);
+    try {
+        WalkPlan p;
+        p.a.base = v->base;
+        p.end_rel = start - v->base;
+        if (!empty && (rc = walk_sweep(v, start, budget, s, &p))) return rc;
+        if ((rc = walk_sizes(v, p, o, keys_cap, values_cap, entries_cap, n_out, key_bytes, value_bytes, end_off, stop)))
+            return rc;
+        if (walk_any(o) && (rc = walk_fill(&p, o, s))) return rc;
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+int vbf_vlog_walk_host(const vbf_vlog* v, uint64_t start, uint64_t budget, uint64_t* entry_off, uint32_t* val_offsets,
+                       uint8_t* keys, uint64_t keys_cap, uint64_t* key_off, uint8_t* values, uint64_t values_cap,
+                       uint64_t* value_off, int64_t* created_ms, uint8_t* tombstones, uint64_t entries_cap,
+                       uint64_t* n_out, uint64_t* key_bytes, uint64_t* value_bytes, uint64_t* end_off, int* stop) {
+    int rc = walk_check(v, start, n_out, key_bytes, value_bytes, end_off, stop);
+    if (rc) return rc;
+    if (start - v->base == v->len) {  // nothing to walk: no device work
+        if (entry_off) entry_off[0] = start;
+        if (key_off) key_off[0] = 0;
+        if (value_off) value_off[0] = 0;
+        return ok();
+    }
+    try {
+        HOST_CALL(call, v->device);
+        WalkPlan p;
+        if ((rc = walk_sweep(v, start, budget, call.s, &p))) return rc;
+        vbf::WalkOut h{};  // the caller's arrays, for the capacity rule
+        h.entry_off = entry_off;
+        h.val_offsets = val_offsets;
+        h.keys = keys;
+        h.key_off = key_off;
+        h.values = values;
+        h.value_off = value_off;
+        h.created = created_ms;
+        h.tomb = tombstones;
+        if ((rc = walk_sizes(v, p, h, keys_cap, values_cap, entries_cap, n_out, key_bytes, value_bytes, end_off, stop)))
+            return rc;
+        if (!walk_any(h)) return call.finish();
+        const uint64_t n = p.n;
+        DevImage img;  // entry_off | val_offsets | keys | key_off | values | value_off | created | tombstones
+        const auto p_eo = img.add<uint64_t>(n + 1, entry_off);
+        const auto p_vo = img.add<uint32_t>(n, val_offsets);
+        const auto p_keys = img.add<uint8_t>(p.kb, keys);
+        const auto p_ko = img.add<uint64_t>(n + 1, key_off);
+        const auto p_vals = img.add<uint8_t>(p.vb, values);
+        const auto p_vof = img.add<uint64_t>(n + 1, value_off);
+        const auto p_cr = img.add<int64_t>(n, created_ms);
+        const auto p_tb = img.add<uint8_t>(n, tombstones);
+        if ((rc = img.alloc(call, kWsVlogWalkOut))) return rc;
+        vbf::WalkOut o{};
+        o.entry_off = img.ptr(p_eo);
+        o.val_offsets = img.ptr(p_vo);
+        o.keys = img.ptr(p_keys);
+        o.key_off = img.ptr(p_ko);
+        o.values = img.ptr(p_vals);
+        o.value_off = img.ptr(p_vof);
+        o.created = img.ptr(p_cr);
+        o.tomb = img.ptr(p_tb);
+        if ((rc = walk_fill(&p, o, call.s))) return rc;
+        if ((rc = call.down(entry_off, o.entry_off, n + 1)) || (rc = call.down(val_offsets, o.val_offsets, n)) ||
+            (rc = call.down(keys, o.keys, p.kb)) || (rc = call.down(key_off, o.key_off, n + 1)) ||
+            (rc = call.down(values, o.values, p.vb)) || (rc = call.down(value_off, o.value_off, n + 1)) ||
+            (rc = call.down(created_ms, o.created, n)) || (rc = call.down(tombstones, o.tomb, n)))
+            return rc;
+        return call.finish();
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
 }
 
 }  // extern "C"

@@ -259,6 +259,64 @@ struct VlogEncArgs {
 };
 hipError_t vlog_enc_check(const VlogEncArgs& a, hipStream_t s);
 hipError_t vlog_encode(const VlogEncArgs& a, hipStream_t s);
+// The walk of the value log (vbf_vlog_walk.hip).  The window is walked in segments of at most
+// kWalkSegment bytes, a segment in tiles of kWalkTile bytes, the tiles in groups of kWalkGroup.
+// Positions inside a segment are u32 relative to its first byte, kWalkOut = none / outside.
+constexpr uint32_t kWalkTile = 4096;
+constexpr uint32_t kWalkGroup = 32;
+constexpr uint32_t kWalkSegment = 8u << 20;
+constexpr uint32_t kWalkSlots = 256;  // entry slots per tile (at most kWalkTile / 17 + 1 = 241 are used)
+constexpr uint32_t kWalkOut = 0xFFFFFFFFu;
+static_assert(kWalkSegment % (kWalkTile * kWalkGroup) == 0, "whole groups per segment");
+struct WalkRes {           // one segment's result, read back by the host
+    uint64_t n, kbytes, vbytes;  // entries, key bytes, value bytes
+    uint64_t end;                // window position where the walk left the segment's last entered tile
+    uint64_t last_entry;         // window position of the last entry (n > 0)
+    uint32_t torn, last_tile;    // the entry at `end` is cut by the window's end; the last tile entered
+};
+struct WalkArgs {
+    const uint8_t* bytes;  // the log's bytes [base, base + len)
+    uint64_t len, base;
+    uint64_t seg0;         // window position of the segment's first byte (a multiple of kWalkTile)
+    uint32_t ntiles, q0;   // tiles of the segment; the entry position, relative to seg0, in tile 0
+    uint64_t cap;          // successors at or beyond it leave the segment: min(segment end, len, lim)
+    uint64_t lim;          // entries start below it (the budget rule, in window positions)
+    uint32_t* exit;        // [ntiles * kWalkTile] (hop pass)
+    uint32_t* gexit;       // [groups * kWalkTile] (group pass)
+    uint32_t* tentry;      // [ntiles] entry position of each tile, kWalkOut: not entered (entry pass)
+    uint16_t* pos;         // [ntiles * kWalkSlots] entry starts within the tile (mark pass)
+    uint16_t* kpre;        // [ntiles * kWalkSlots] key bytes of the tile's entries before this one
+    uint64_t* cnt;         // [ntiles + 1] per tile: entries, key bytes, value bytes; [ntiles] = 0
+    uint64_t* ksum;
+    uint64_t* vsum;
+    uint64_t* tend;        // [ntiles] where the tile's walk stopped, [ntiles] whether on a torn entry
+    uint32_t* ttorn;
+    uint64_t* cbase;       // [ntiles + 1] exclusive scans of cnt / ksum / vsum
+    uint64_t* kbase;
+    uint64_t* vbase;
+    uint64_t* ko;          // [entries + 1] per entry of the segment: the key's place in the segment's
+    uint64_t* ks;          // key bytes and its position in the window; the same for the value (emit)
+    uint64_t* vo;
+    uint64_t* vs;
+    WalkRes* res;
+};
+struct WalkOut {           // the caller's arrays (each may be NULL) and the segment's place in them
+    uint64_t* entry_off;
+    uint32_t* val_offsets;
+    uint8_t* keys;
+    uint64_t* key_off;
+    uint8_t* values;
+    uint64_t* value_off;
+    int64_t* created;
+    uint8_t* tomb;
+    uint64_t j0, k0, v0;            // entries, key bytes and value bytes of the segments before
+    uint64_t n_seg, kb_seg, vb_seg; // this segment's
+};
+// hop, group, entry, mark, the three scans and the result, queued on s; scan_tmp: scan_u64's scratch
+// for ntiles + 1 items.
+hipError_t walk_passes(const WalkArgs& a, void* scan_tmp, size_t scan_bytes, hipStream_t s);
+hipError_t walk_emit(const WalkArgs& a, const WalkOut& o, hipStream_t s);
+hipError_t walk_tail(const WalkOut& o, uint64_t n, uint64_t end_off, uint64_t kb, uint64_t vb, hipStream_t s);
 // Batched probe across SSTs (vbf_multi.hip).
 struct MultiSst {
     const uint32_t* words;

@@ -1,0 +1,91 @@
+"""The garbage collector's handler over SSTs, by composition of the batched device paths.
+
+GC::gc_handler (src/gc/garbage_collector.rs:168-262) reads a chunk of the value log from its tail
+(read_chunk_to_garbage_collect, src/fs/mod.rs:579-651), looks every entry's key up (GC::get,
+garbage_collector.rs:429-469), sorts the entries into valid and invalid (:203-214) and, when any is
+invalid, appends a `tail` entry and the valid entries to the log (:231-241) and puts them into the
+GC table (:245-251, GC::put :404-419).  Here:
+
+  collect(vlog, tables, tail, chunk_bytes, log_size, now_ms, filters=None, overlay=None) -> GcResult or None
+      ValueLog.read_chunk (vbf_vlog_walk_*), then Table.get_many over `tables` (step 3 of GC::get),
+      then ValueLog.get_many for the most recent values, then ValueLog.encode for the bytes to append.
+
+`overlay` maps a key to (val_offset, created_ms, tombstone): what steps 1 and 2 of GC::get found in
+the GC memtable and the read-only memtables.  The caller folds those two steps (the active table
+first, else the most recent of the read-only ones); a key found there skips the tables.
+
+An entry is invalid when the lookup ends in the reference's NotFoundInDB -- no table holds the key,
+the winning entry is a tombstone, or the fetch finds a tombstone or nothing (get_value_from_vlog,
+:524-537) --, when entry.created_at < the winner's creation time, or when the fetched value is "*"
+(:205-208).  Every other entry is valid and carries the most recent value, not its own (:210).
+With no invalid entry nothing is produced (:228-230): collect returns None.
+
+Order: the reference pushes valid entries from concurrent tasks (tokio::spawn per entry, :185-217),
+so their order in its log is not fixed.  Here they keep the chunk's order.
+
+Out of scope: hole punching, fsync, the memtables themselves, timers.  The per-entry flags are
+plain numpy on arrays that are already on the host.
+"""
+import struct
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import table as _table
+from .vlog import BAD, KEY_MISMATCH, VALUE, ValueLog
+
+TOMB_STONE_MARKER = b"*"
+TAIL_ENTRY_KEY = b"tail"
+
+
+@dataclass
+class GcResult:
+    invalid: np.ndarray           # the chunk's invalid entries, as indices into the chunk
+    total_bytes_read: int         # the chunk's bytes: the punch hole's length (:257)
+    new_tail: int                 # tail + total_bytes_read (:231)
+    append: bytes                 # what to write at log_size: the `tail` entry, then the valid entries
+    put_keys: list                # the puts for the GC table, in the order appended (GC::put):
+    put_val_offsets: np.ndarray   # uint32: each appended entry's position
+    put_created_ms: np.ndarray    # int64: now_ms
+    put_tombstones: np.ndarray    # uint8: 1 where the value is empty (:411)
+
+
+def collect(vlog, tables, tail, chunk_bytes, log_size, now_ms, filters=None, overlay=None):
+    """One run of gc_handler over the chunk at `tail`; `log_size` is the file's size (where the
+    appends go), `now_ms` stands for Utc::now() in every entry written.  The most recent values are
+    read from `vlog`, whose window must hold them.  Raises ValueError when a most recent entry is BAD
+    (outside the window or cut by its end)."""
+    tail, log_size, now_ms = int(tail), int(log_size), int(now_ms)
+    w = vlog.read_chunk(int(chunk_bytes), tail)
+    n = w.n
+    total = w.end_off - tail
+    keys = [w.key(i) for i in range(n)] if overlay else None
+    res = _table.get_many(w.keys, tables, filters) if n else None
+    found = np.zeros(n, np.uint8) if res is None else res.found.copy()
+    vo = np.zeros(n, np.uint32) if res is None else res.val_offsets.copy()
+    # created_at is a u64 of milliseconds in data.db and in the log; one signed view for both
+    cr = np.zeros(n, np.int64) if res is None else res.created_ms.astype(np.uint64).view(np.int64).copy()
+    if overlay:
+        for i, k in enumerate(keys):
+            hit = overlay.get(k)
+            if hit is not None:
+                vo[i], cr[i], found[i] = int(hit[0]), int(hit[1]), _table.FOUND_TOMBSTONE if hit[2] else _table.FOUND_LIVE
+    got = vlog.get_many(vo, found=found)
+    if np.isin(got.status, (BAD, KEY_MISMATCH)).any():
+        i = int(np.flatnonzero(np.isin(got.status, (BAD, KEY_MISMATCH)))[0])
+        raise ValueError("gc: the most recent entry of chunk entry %d, at %d, is not a whole entry of the log" % (i, vo[i]))
+    lens = np.diff(got.value_off.astype(np.int64))
+    star = np.zeros(n, bool)
+    one = np.flatnonzero((got.status == VALUE) & (lens == 1))
+    star[one] = got.values[got.value_off[one].astype(np.int64)] == TOMB_STONE_MARKER[0]
+    invalid = (got.status != VALUE) | (w.created_ms < cr) | star
+    if not invalid.any():
+        return None
+    new_tail = tail + total
+    valid = np.flatnonzero(~invalid)
+    put_keys = [TAIL_ENTRY_KEY] + [w.key(int(i)) for i in valid]
+    values = [struct.pack("<Q", new_tail)] + [got.value(int(i)) for i in valid]
+    created = np.full(len(put_keys), now_ms, np.int64)
+    append, offs = ValueLog.encode(put_keys, values, created_ms=created, base=log_size, device=vlog.device)
+    tomb = np.array([len(v) == 0 for v in values], np.uint8)
+    return GcResult(np.flatnonzero(invalid).astype(np.uint64), total, new_tail, append, put_keys, offs, created, tomb)

@@ -14,6 +14,8 @@ velarixdb_amd/csrc/vbf_memtable.hip).
   put_many(keys, values, created_ms, tombstones=None, base=0, filter=None)
       -> (log bytes, FlushResult)      ValueLog.encode, then flush with its val_offsets
   flush_to_dir(sst_dir, keys, val_offsets, ...)             flush into sst_dir/data.db and index.db
+  recover_puts(vlog, head_offset)      -> (keys, val_offsets, created_ms, tombstones): the recovered
+                                       log's entries after the head entry, ready for sort_ids / flush
   BloomFilter.insert_many(keys)        the memtable's filter step, see filter.py
 
 `filter` (a device-resident BloomFilter on `device`) takes MemTable::insert's filter step over
@@ -101,6 +103,21 @@ def put_many(keys, values, created_ms, tombstones=None, base=0, filter=None, dev
     b = _batch(keys)
     log, vo = ValueLog.encode(b, values, created_ms=created_ms, tombstones=tombstones, base=base, device=device)
     return log, flush(b, vo, created_ms=created_ms, tombstones=tombstones, filter=filter, device=device)
+
+
+def recover_puts(vlog, head_offset):
+    """The data side of recover_memtable (src/db/recovery.rs:245-286): the value log's entries from
+    `head_offset` on (ValueLog::recover, a ValueLog.walk on the device) without the first one, which
+    is the most recent entry already in an SST (recovery.rs:261-264), as the puts that rebuild the
+    memtables -> (keys HostBatch, val_offsets u32, created_ms i64, tombstones u8), in log order,
+    ready for sort_ids / flush.  A torn last entry (a crash mid-append) is left out.  Cutting the
+    stream into memtables by capacity stays with the caller."""
+    w = vlog.walk(start=head_offset, values=False)
+    if w.n == 0:
+        return HostBatch(np.zeros(0, np.uint8), np.zeros(1, np.uint64), 0, 0, 1), np.zeros(0, np.uint32), \
+            np.zeros(0, np.int64), np.zeros(0, np.uint8)
+    keys = HostBatch(w.keys.data, w.keys.offsets[1:].copy(), 0, w.n - 1, w.keys.len_prefix)
+    return keys, w.val_offsets[1:].copy(), w.created_ms[1:].copy(), w.tombstones[1:].copy()
 
 
 def flush_to_dir(sst_dir, keys, val_offsets, created_ms=None, tombstones=None, filter=None, device=0):

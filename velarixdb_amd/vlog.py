@@ -18,6 +18,10 @@ vbf_vlog_*, velarixdb_amd/csrc/vbf_vlog.hip).
       (outside the window or cut by its end), KEY_MISMATCH (keys given and the entry holds another)
   ValueLog.encode(keys, values, created_ms=None, tombstones=None, base=0) -> (log bytes, val_offsets)
       what append writes for a batch of puts when the file's size is `base`
+  vlog.walk(start=None, budget=None, values=True) -> Walk   the entries from `start` on, in file order
+      (C ABI vbf_vlog_walk_*, velarixdb_amd/csrc/vbf_vlog_walk.hip); its two named uses:
+  vlog.recover(head)            ValueLog::recover (fs/mod.rs:520-577)
+  vlog.read_chunk(budget, tail) read_chunk_to_garbage_collect (fs/mod.rs:579-651)
 """
 import ctypes
 from dataclasses import dataclass
@@ -25,9 +29,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import (VBF_VLOG_BAD, VBF_VLOG_KEY_MISMATCH, VBF_VLOG_NONE, VBF_VLOG_SKIPPED, VBF_VLOG_TOMBSTONE,
-                   VBF_VLOG_VALUE, VbfError, call, lib)
+                   VBF_VLOG_VALUE, VBF_WALK_BUDGET, VBF_WALK_END, VBF_WALK_TORN, VbfError, call, lib)
 from .filter import _raise
-from .keys import HostBatch, pack
+from .keys import HostBatch, pack, pack_offsets
 from .sst import _buf
 
 SKIPPED, VALUE, TOMBSTONE, NONE, BAD, KEY_MISMATCH = (VBF_VLOG_SKIPPED, VBF_VLOG_VALUE, VBF_VLOG_TOMBSTONE,
@@ -45,6 +49,39 @@ class Values:
         if self.status[j] != VALUE:
             return None
         return self.values[int(self.value_off[j]):int(self.value_off[j + 1])].tobytes()
+
+
+WALK_END, WALK_BUDGET, WALK_TORN = VBF_WALK_END, VBF_WALK_BUDGET, VBF_WALK_TORN
+_NO_BUDGET = 2**64 - 1
+
+
+@dataclass
+class Walk:
+    entry_off: np.ndarray   # uint64 [n + 1]: the entries' file positions, then end_off
+    keys: HostBatch         # the entries' keys, in file order
+    values: np.ndarray      # uint8: the entries' own values back to back, or None (values=False)
+    value_off: np.ndarray   # uint64 [n + 1]: entry i's value = values[value_off[i] .. value_off[i+1])
+    created_ms: np.ndarray  # int64: the stored created_at
+    tombstones: np.ndarray  # uint8: 1 iff the entry's byte is 1
+    end_off: int            # where the walk stopped: the bytes read are end_off - start
+    stop: int               # WALK_END, WALK_BUDGET or WALK_TORN (end_off is then the torn entry)
+
+    @property
+    def n(self):
+        return self.created_ms.size
+
+    @property
+    def val_offsets(self):
+        """entry_off[:n] as uint32: what memtable.flush and get_many take (ValueError at 2^32 or beyond)."""
+        if self.n and int(self.entry_off[self.n - 1]) >= 2**32:
+            raise ValueError("an entry lies at or beyond 2^32")
+        return self.entry_off[:self.n].astype(np.uint32)
+
+    def key(self, i):
+        return self.keys.data[int(self.keys.offsets[i]):int(self.keys.offsets[i + 1])].tobytes()
+
+    def value(self, i):
+        return self.values[int(self.value_off[i]):int(self.value_off[i + 1])].tobytes()
 
 
 def _key_ptrs(keys):
@@ -130,6 +167,39 @@ class ValueLog:
         except VbfError as e:
             _raise("vlog_get", e)
         return res
+
+    def walk(self, start=None, budget=None, values=True):
+        """The entries from file position `start` (the window's base) on, in file order, until the end
+        of the log, a torn entry, or the entry that brings the bytes read to `budget` or more (None:
+        no budget).  values=False leaves the value bytes behind (value_off is still filled).  One size
+        query, then one filling call."""
+        start = self.base if start is None else int(start)
+        budget = _NO_BUDGET if budget is None else int(budget)
+        sc = [ctypes.c_uint64() for _ in range(4)]
+        stop = ctypes.c_int()
+        tail = [ctypes.byref(x) for x in sc] + [ctypes.byref(stop)]
+        try:
+            call("vbf_vlog_walk_host", self._h, start, budget, None, None, None, 0, None, None, 0, None, None, None, 0,
+                 *tail)
+            n, kb, vb = sc[0].value, sc[1].value, sc[2].value
+            eo, ko, vo = (np.zeros(n + 1, np.uint64) for _ in range(3))
+            kd, vd = np.zeros(kb, np.uint8), np.zeros(vb if values else 0, np.uint8)
+            cr, tb = np.zeros(n, np.int64), np.zeros(n, np.uint8)
+            vp = lambda x: x.ctypes.data if x.size else None
+            call("vbf_vlog_walk_host", self._h, start, budget, vp(eo), None, vp(kd), kb, vp(ko), vp(vd), vd.size, vp(vo),
+                 vp(cr), vp(tb), n, *tail)
+        except VbfError as e:
+            _raise("vlog_walk", e)
+        return Walk(eo, pack_offsets(kd, ko), vd if values else None, vo, cr, tb, sc[3].value, stop.value)
+
+    def recover(self, head):
+        """ValueLog::recover(head) (fs/mod.rs:520-577): every entry from the head offset to the end."""
+        return self.walk(start=head)
+
+    def read_chunk(self, budget, tail):
+        """read_chunk_to_garbage_collect(budget, tail) (fs/mod.rs:579-651): entries from the tail until
+        at least `budget` bytes were read; the bytes read are walk.end_off - tail."""
+        return self.walk(start=tail, budget=budget)
 
     @staticmethod
     def encode(keys, values, created_ms=None, tombstones=None, base=0, device=0):
