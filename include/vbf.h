@@ -478,7 +478,9 @@ int vbf_filter_rebuild_from_sst_host(vbf_filter* f, const uint8_t* data, uint64_
  * without bounds every key reaches every filter, with bounds only the keys inside that SST's
  * range do (one extra readback when such a filter is present).  Host-resident filters are
  * rejected (vbf_filter_migrate them to the device first).
- * _dev: keys / offsets / out on that device, queued on `stream`.  _host: host buffers, synchronous. */
+ * _dev: keys / offsets / out on that device, queued on `stream` after one synchronisation of it (the
+ * upload of the filters' table and of the bounds, whose host sources are the caller's).  _host: host
+ * buffers, synchronous. */
 int vbf_multi_probe_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
                         int len_prefix, uint32_t nsst, const vbf_filter* const* filters,
                         const uint8_t* bounds, const uint64_t* bounds_off, uint8_t* out, void* stream);

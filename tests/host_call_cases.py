@@ -326,6 +326,34 @@ def rebuild_jobs(ora, threads=THREADS, rounds=ROUNDS):
     return [[job(t, i) for i in rotation(range(len(REBUILD_SIZES)), t, rounds)] for t in range(threads)]
 
 
+P_BUILD = 1e-4                     # k = 19
+REBUILD_BUILD_SIZES = (240_000, 3_000)  # 4 560 000 bit indices, past the 2^22 at which AUTO builds partitioned; 57 000
+BUILD_THREADS, BUILD_ROUNDS = 2, 12
+
+
+@functools.lru_cache(maxsize=None)
+def rebuild_build_case(ora, thread, i):
+    """A table of thread `thread`'s own with REBUILD_BUILD_SIZES[i] entries and the filter
+    BloomFilter::new(P_BUILD, n) rebuilt from it: (data, index), (n, m, k, words)."""
+    from velarixdb_amd.keys import pack_offsets
+    n = REBUILD_BUILD_SIZES[i]
+    data, index = counter_table(ora, n, 40 + 10 * i + thread)
+    keys, offs, *_ = ora.sst_decode(np.frombuffer(data, np.uint8))
+    m = ora.num_bits(n, P_BUILD)
+    k = ora.num_hash(m, n)
+    return (data, index), (n, m, k, ora.build_words(pack_offsets(keys, offs), m, k, threads=8))
+
+
+def rebuild_build_jobs(ora, threads=BUILD_THREADS, rounds=BUILD_ROUNDS):
+    """vbf_filter_rebuild_from_sst_host where the build behind the decode is the partitioned one: the
+    large and the small table alternate, thread 1 a round behind thread 0, so in every round one
+    thread's rebuild takes the partitioned build's workspace and the other's the atomic build."""
+    def job(t, i):
+        files, want = rebuild_build_case(ora, t, i)
+        return Job("rebuild_build", "t%d/sst%d" % (t, i), (t, i) + files, want, want[0])
+    return [[job(t, i) for i in rotation(range(len(REBUILD_BUILD_SIZES)), t, rounds)] for t in range(threads)]
+
+
 # ---- the one-shot build and probe (they take the staging lock, not the host-call lock) ----------
 
 ONE_SHOT = ((1_000, 12), (60_000, 16), (257, 0), (9_000, 33))  # (keys, stride; 0 = lengths 0..40)

@@ -59,6 +59,7 @@ class Ctx:
             self.probe_ranges.append(ranges)
         self.rebuild_filters = {(t, i): vbf.BloomFilter(hc.P, n)
                                 for t in range(hc.THREADS) for i, n in enumerate(hc.REBUILD_SIZES)}
+        self.build_filters = {}  # (thread, SST) -> the filter of a rebuild_build job
         self.packed = {}       # job ident -> HostBatch: packed once, in the serial run
         self.sst_tables = {}   # merge case -> [SstEntries]
         self.lock_filter = None
@@ -149,6 +150,14 @@ def run_rebuild(job, ctx):
     return f.rebuild_from_sst(data, index), f.num_bits(), f.no_of_hash_func, f.words()
 
 
+def run_rebuild_build(job, ctx):
+    t, i, data, index = job.args
+    if (t, i) not in ctx.build_filters:  # created in the serial control, which runs first
+        ctx.build_filters[t, i] = ctx.vbf.BloomFilter(hc.P_BUILD, job.size)
+    f = ctx.build_filters[t, i]
+    return f.rebuild_from_sst(data, index), f.num_bits(), f.no_of_hash_func, f.words()
+
+
 def run_build_host(job, ctx):
     from velarixdb_amd._lib import call
     keys, m, k = job.args
@@ -205,7 +214,7 @@ RUN = {
     "encode": run_encode, "decode": run_decode, "open": run_open, "get": _get,
     "get_filtered": lambda job, ctx: _get(job, ctx, ctx.filters), "scan": run_scan,
     "scan_two_calls": run_scan_two_calls, "merge": run_merge, "write": run_write, "probe": run_probe,
-    "rebuild": run_rebuild, "build_host": run_build_host, "probe_host": run_probe_host, "flush": run_flush,
+    "rebuild": run_rebuild, "rebuild_build": run_rebuild_build, "build_host": run_build_host, "probe_host": run_probe_host, "flush": run_flush,
     "lock_set": run_lock_set, "lock_probe": run_lock_probe, "lock_rebuild": run_lock_rebuild,
     "lock_get": lambda job, ctx: _get(job, ctx, [ctx.lock_filter] + ctx.filters[1:]),
 }
@@ -316,15 +325,18 @@ FAMILIES = {
     "write": (hc.write_jobs, "kWsCompactIn, kWsCompact, kWsGather, kWsCompactOut, kWsSstEnc"),
     "probe": (hc.probe_jobs, "kWsMultiKeys, kWsMulti"),
     "rebuild": (hc.rebuild_jobs, "kWsSstInput, kWsSstKeys, kWsSstScratch"),
+    "rebuild_build": (hc.rebuild_build_jobs, "kWsSstInput, kWsSstKeys, kWsSstScratch, kWsBuild"),
 }
 # kWsBuild, which compact_write and rebuild_from_sst also reach, is used only by builds of 2^22 bit
-# indices or more (the partitioned build); the tables here stay far below that, so it is not covered.
+# indices or more (the partitioned build).  The tables of the other families stay far below that;
+# "rebuild_build" (two threads) alternates a table of 240 000 entries at k = 19, whose rebuild takes
+# the partitioned build and with it kWsBuild, with one of 3 000, whose rebuild builds with atomics.
 
 
 @pytest.mark.parametrize("family", list(FAMILIES))
 def test_same_entry_point_different_inputs(ctx, family):
-    """Four threads in one entry point, sizes rotating per round: each thread's staged inputs share
-    FAMILIES[family][1] with the three others', at a different size each."""
+    """Four threads (two for rebuild_build) in one entry point, sizes rotating per round: each thread's
+    staged inputs share FAMILIES[family][1] with the others', at a different size each."""
     both(FAMILIES[family][0](ctx.ora), ctx)
 
 

@@ -141,6 +141,24 @@ def test_rebuilds(ora):
     assert len(filters) == 16  # a filter per (thread, SST): no two threads write one filter
 
 
+def test_rebuilds_that_take_the_partitioned_build(ora):
+    per_thread = hc.rebuild_build_jobs(ora)
+    assert len(per_thread) == hc.BUILD_THREADS == 2 and all(len(jobs) == hc.BUILD_ROUNDS == 12 for jobs in per_thread)
+    for r in range(hc.BUILD_ROUNDS):
+        a, b = per_thread[0][r], per_thread[1][r]
+        assert {a.size, b.size} == {240_000, 3_000}, r  # one of each kind in every round
+        assert hc.fingerprint(a.args[2:]) != hc.fingerprint(b.args[2:]) and hc.fingerprint(a.want) != hc.fingerprint(b.want)
+    for jobs in per_thread:
+        assert all(x.size != y.size for x, y in zip(jobs, jobs[1:]))  # alternating
+        for j in jobs[:2]:
+            n, m, k, words = j.want
+            assert k == 19 and m == ora.num_bits(n, hc.P_BUILD) and words.size == (m + 31) // 32
+            assert (n * k >= 2**22) == (n == 240_000)  # AUTO's threshold between the two builds
+            assert 0 < int(np.unpackbits(words.view(np.uint8)).sum()) < m
+    tables = {j.args[:2] for jobs in per_thread for j in jobs}
+    assert len(tables) == 4  # a filter per (thread, SST)
+
+
 def test_one_shot_and_flush_jobs(ora):
     for j in hc.build_host_jobs(ora)[:4]:
         keys, m, k = j.args
