@@ -49,6 +49,12 @@
  *   Flusher::flush                     src/flush/flusher.rs:37-64  -> vbf_flush_write_host
  *   Table::write_to_file (a memtable)  src/sst/table.rs:258-326    -> vbf_flush_write_host
  *   DataStore::put (log, then insert)  src/db/store.rs:215-243     -> vbf_vlog_encode_* + vbf_flush_write_host
+ *   GC::gc_handler                     src/gc/garbage_collector.rs:168-262 -> vbf_gc_collect_host
+ *   GC::get                            src/gc/garbage_collector.rs:429-469 -> vbf_gc_collect_host (overlay, tables, log)
+ *   write_tail_to_disk                 src/gc/garbage_collector.rs:265-275 -> vbf_gc_collect_host (put 0 of `append`)
+ *   write_valid_entries_to_vlog        src/gc/garbage_collector.rs:304-317 -> vbf_gc_collect_host (the rest of `append`)
+ *   GC::put                            src/gc/garbage_collector.rs:404-419 -> vbf_gc_collect_host (put_val_offsets,
+ *                                                                             put_tombstones)
  *
  * Key batches.  `keys` holds the key bytes back to back.  When `offsets` is non-NULL it has
  * n+1 nondecreasing entries and key j is keys[offsets[j] .. offsets[j+1]) (positions are
@@ -70,7 +76,7 @@
  * words copies take turns on the device's two staging streams, and the other `_host` entry points
  * (sst_decode, sst_encode, rebuild_from_sst, multi_probe, compact_merge, compact_write,
  * table_open, table_get, table_scan, vlog_open, vlog_get, vlog_encode, vlog_walk, memtable_sort,
- * flush_write, and filter_insert_host on a device-resident filter) take turns on its shared
+ * flush_write, gc_collect, and filter_insert_host on a device-resident filter) take turns on its shared
  * stream, each from its first upload to its last download; the two groups overlap each other, and
  * devices never wait for each other.  A call that spans several devices (vbf_multi_probe_host over filters on several GPUs)
  * holds one device at a time.  Locks are taken filters first (in address order), then the device.
@@ -114,7 +120,8 @@ int vbf_device_count(int* count);
  * tables + validation), 19 table get, 20 table scan bounds + rank (with their scans), 21 table scan
  * emit + key copy, 22 value-log fetch sizes + scan, 23 value-log fetch copy, 24 value-log encode
  * (its check and its copy), 25 memtable tile sort (with its prefix pass), 26 memtable merge levels
- * + keep flags + select, 27 filter insert (count passes and the build).
+ * + keep flags + select, 27 filter insert (count passes and the build), 28 GC judge (with its overlay
+ * search, scan and select), 29 GC emit.
  * vbf_profile_read synchronizes, returns per-phase summed ms and launch counts, and resets; it
  * fills the first `nphases` phases, so a caller built against a shorter list keeps working (the
  * later phases' records are dropped). */
@@ -910,6 +917,82 @@ int vbf_vlog_walk_host(const vbf_vlog* v, uint64_t start, uint64_t budget, uint6
                        uint64_t values_cap, uint64_t* value_off, int64_t* created_ms, uint8_t* tombstones,
                        uint64_t entries_cap, uint64_t* n_out, uint64_t* key_bytes, uint64_t* value_bytes,
                        uint64_t* end_off, int* stop);
+
+/* ---- the garbage collector's handler over one chunk, in one device pass ----
+ * GC::gc_handler (gc/garbage_collector.rs:168-262) reads a chunk of the log from its tail (:176-179),
+ * looks every entry's key up (GC::get, :429-469), sorts the entries into valid and invalid (:203-214)
+ * and, when any is invalid, appends a `tail` entry (write_tail_to_disk, :265-275) and the valid
+ * entries (write_valid_entries_to_vlog, :304-317) to the log and puts them into the GC table
+ * (:245-251, GC::put :404-419).  vbf_gc_collect_host does the data side of that over an open vbf_vlog
+ * and open tables: the log window and the tables are already on the device, so only the overlay goes
+ * up and only the verdicts, the bytes to append and the puts come down.  The chunk's own values are
+ * never materialised: a valid entry carries the MOST RECENT value (:210), which is copied from its
+ * place in the window straight into `append`.
+ *
+ * Chunk: vbf_vlog_walk_* from `tail` with budget `chunk_bytes`; *n_chunk, *end_off and *stop are the
+ * walk's, the total bytes read (the punch hole's length, :257) is *end_off - tail.  A torn tail ends
+ * the chunk as it ends the walk; the entries before it are judged.  tail == base + len is VBF_OK with
+ * every count 0 and no device work.
+ * Lookup: chunk entry i's key is first searched in the overlay -- ov_n strictly ascending keys
+ * (`Ord for [u8]`), key k = ov_keys[ov_off[k] .. ov_off[k+1]) (the layout of the compaction's
+ * tombstone map: ov_off has ov_n + 1 absolute positions), with ov_val_offsets[k], ov_created_ms[k],
+ * ov_tombstones[k].  It stands for steps 1 and 2 of GC::get (:440-463), the GC table and the
+ * read-only memtables, which the caller folds (the active table first, else the most recent of the
+ * read-only ones); a hit decides the entry whatever its time.  Otherwise vbf_table_get_* over
+ * `tables` decides (step 3), the candidates first cut by `filters` when given (one per table, or
+ * NULL), exactly as in vbf_table_get_host.
+ * verdict[i] is the first of these tests that applies, in this order: */
+#define VBF_GC_VALID 0          /* kept: re-appended with its most recent value (:210)                 */
+#define VBF_GC_ABSENT 1         /* neither the overlay nor any table holds the key (NotFoundInDB)      */
+#define VBF_GC_DELETED 2        /* the winner (overlay or table) is a tombstone (:442-444, :459, :505) */
+#define VBF_GC_LOG_NONE 3       /* the winner's offset is >= base + len: Ok(None) (:524-537)           */
+#define VBF_GC_LOG_TOMBSTONE 4  /* the most recent log entry's byte is 1 (:531-533)                    */
+#define VBF_GC_OLDER 5          /* entry.created_at < the winner's creation time (:205)                */
+#define VBF_GC_STAR 6           /* the most recent value is "*" (:206)                                 */
+/* The window checks on the most recent entry are vbf_vlog_get_*'s.  created_at on both sides is
+ * compared as the signed 64-bit value the reference's DateTime holds; equal times are valid.  A most
+ * recent entry that is BAD (before base, or its header or body crosses base + len) fails the call
+ * with VBF_EINVAL, the message naming the first such chunk entry and its offset; no output array is
+ * touched.  *n_invalid counts the entries whose verdict is not VBF_GC_VALID.
+ * Nothing to collect: *n_invalid == 0 is VBF_OK with *n_puts = *append_len = 0 (:228-230); verdict
+ * is still filled.
+ * Appended bytes (*n_invalid > 0): `append` holds exactly what vbf_vlog_encode_* with base = log_size
+ * produces for the puts: every created_at is now_ms and every tombstone byte 0 (:265-275, :304-317).
+ * Put 0 has key "tail" and value LE64(tail + total bytes read) (:231-238); after it come the valid
+ * entries in chunk order (this library's reading: the reference's tasks push them in no fixed order,
+ * :185-217), each with its own key and the most recent value.  put_val_offsets[j] is put j's
+ * position (u32), put_tombstones[j] is 1 iff its value is empty (GC::put :411), put_ids[j] the chunk
+ * index of put j and 0xFFFFFFFF for put 0; *n_puts = 1 + the valid entries.  The puts' keys are not
+ * returned apart: put j's key lies in `append` at put_val_offsets[j] - log_size + 17, its length in
+ * the 4 bytes at put_val_offsets[j] - log_size.
+ * Sizes: the six scalars (*n_chunk, *n_invalid, *n_puts, *append_len, *end_off, *stop) are always
+ * written.  Every output array may be NULL; all of them NULL is the size query.  A capacity that is
+ * too small -- entries_cap < *n_chunk with verdict given, puts_cap < *n_puts with a put array given,
+ * append_cap < *append_len with append given -- is VBF_EINVAL with the sizes written and no array
+ * touched.  An appended entry that would start at 2^32 or beyond is VBF_EINVAL, as in
+ * vbf_vlog_encode_*; log_size + 25 > 2^32, where no entry can follow the 29-byte `tail` entry below
+ * 2^32, is rejected before any device work.  At most 2^31 - 2 chunk entries and overlay keys.
+ * Checks that run on the host before any HIP call and before any handle is followed: a NULL scalar
+ * (nothing is written then); after the scalars are written, a NULL log, nsst > 0 with NULL tables or
+ * a NULL element, a NULL filters[i], ov_n > 0 with an overlay array missing, a descending ov_off,
+ * overlay keys not strictly ascending, the log_size rule.  Once the handles are read: `tail` outside
+ * [base, base + len], tables or filters not on the log's device (VBF_EINVAL).
+ * Cost: the walk's passes, one lookup, then three kernels (csrc/vbf_gc.hip) -- the overlay search and
+ * the judge, one lane per chunk entry, and the emit, which divides the bytes to append among the
+ * workgroups as vbf_vlog_get_*'s copy does.  Workspace: 79 bytes per chunk entry plus its key (and
+ * nsst with filters), 1 byte per appended byte and 5 per put, next to the walk's and the lookup's.
+ * Stream synchronisations: the walk's one per 8 MiB segment, the lookup's (its descriptors, and the
+ * filters' table), one for the judge's result, one at the end.  Synchronous, on the log's device;
+ * locks as vbf_table_get_host takes them (the filters first, then the device). */
+int vbf_gc_collect_host(const vbf_vlog* v, uint64_t tail, uint64_t chunk_bytes, uint64_t log_size, int64_t now_ms,
+                        uint32_t nsst, const vbf_table* const* tables, const vbf_filter* const* filters,
+                        const uint8_t* ov_keys, const uint64_t* ov_off, const uint32_t* ov_val_offsets,
+                        const int64_t* ov_created_ms, const uint8_t* ov_tombstones, uint64_t ov_n,
+                        uint8_t* verdict, uint64_t entries_cap,
+                        uint8_t* append, uint64_t append_cap,
+                        uint32_t* put_ids, uint32_t* put_val_offsets, uint8_t* put_tombstones, uint64_t puts_cap,
+                        uint64_t* n_chunk, uint64_t* n_invalid, uint64_t* n_puts, uint64_t* append_len,
+                        uint64_t* end_off, int* stop);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ from .filter import (DEFAULT_FALSE_POSITIVE_RATE, FILTER_FILE_NAME, HOST, BloomF
 from .keys import HostBatch, I32Vec, RawMessage, Usize, pack, pack_fixed, pack_offsets  # noqa: F401
 from .table import GetResult, ScanResult, Table, get_many, get_values, scan_many, scan_values  # noqa: F401
 from .vlog import ValueLog, Values, Walk  # noqa: F401
+from .gc import GcResult, collect_device  # noqa: F401
 from . import compaction, gc, key_range, memtable, sst, table, vlog  # noqa: F401
 
 __version__ = "0.1.0"

@@ -30,6 +30,9 @@ VBF_SCAN_KEEP_TOMBSTONES, VBF_SCAN_END_EXCLUSIVE = 1, 2  # vbf_table_scan_* flag
 (VBF_VLOG_SKIPPED, VBF_VLOG_VALUE, VBF_VLOG_TOMBSTONE, VBF_VLOG_NONE, VBF_VLOG_BAD,
  VBF_VLOG_KEY_MISMATCH) = range(6)
 VBF_WALK_END, VBF_WALK_BUDGET, VBF_WALK_TORN = 0, 1, 2  # vbf_vlog_walk_* stop
+# vbf_gc_collect_host verdict
+(VBF_GC_VALID, VBF_GC_ABSENT, VBF_GC_DELETED, VBF_GC_LOG_NONE, VBF_GC_LOG_TOMBSTONE, VBF_GC_OLDER,
+ VBF_GC_STAR) = range(7)
 
 _u8p = ctypes.c_void_p  # raw pointers (host or device) travel as integers
 _u64 = ctypes.c_uint64
@@ -161,6 +164,10 @@ SIGNATURES = {
     "vbf_filter_insert_dev": (_int, [_vp, _vp, _vp, _u64, _u64, _int, ctypes.POINTER(_u64), _vp]),
     "vbf_flush_write_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64,
                                      ctypes.POINTER(_u64), _vp, ctypes.POINTER(_u64), _int]),
+    "vbf_gc_collect_host": (_int, [_vp, _u64, _u64, _u64, ctypes.c_int64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64,
+                                    _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64),
+                                    ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                    ctypes.POINTER(_u64), ctypes.POINTER(_int)]),
 }
 
 
@@ -214,7 +221,7 @@ def device_count():
 PHASES = ("tile_sort", "transpose", "seg_or", "atomic_build", "probe", "sst_walk", "sst_scan", "sst_emit",
           "merge_levels", "fold", "select", "probe_pack", "probe_seg", "probe_out", "enc_tile", "enc_scan",
           "enc_index", "enc_data", "table_open", "table_get", "scan_rank", "scan_emit", "vlog_sizes", "vlog_copy",
-          "vlog_encode", "mem_sort", "mem_merge", "filter_insert")
+          "vlog_encode", "mem_sort", "mem_merge", "filter_insert", "gc_judge", "gc_emit")
 
 
 def profile_read():

@@ -181,6 +181,8 @@ enum WsSlot {
     kWsFilterInsertIO = 30,
     kWsVlogWalk = 31,
     kWsVlogWalkOut = 32,
+    kWsGc = 33,
+    kWsGcOut = 34,
 };
 struct Workspace {
     int device;
@@ -3822,6 +3824,20 @@ int table_lookup(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, 
 
 int table_no_memory() { return fail(VBF_ENOMEM, "out of host memory"); }
 
+// The tables' own key ranges in multi_probe's layout (smallest, biggest per table): the candidate
+// cut of a lookup that is given filters.
+void table_bounds(uint32_t nsst, const vbf_table* const* tables, std::vector<uint8_t>* bounds,
+                  std::vector<uint64_t>* boff) {
+    boff->assign(1, 0);
+    for (uint32_t i = 0; i < nsst; ++i) {
+        bounds->insert(bounds->end(), tables[i]->smallest.begin(), tables[i]->smallest.end());
+        boff->push_back(bounds->size());
+        bounds->insert(bounds->end(), tables[i]->biggest.begin(), tables[i]->biggest.end());
+        boff->push_back(bounds->size());
+    }
+    bounds->push_back(0);  // never NULL
+}
+
 }  // namespace
 
 extern "C" {
@@ -3974,14 +3990,8 @@ int vbf_table_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t st
         if (offsets && ((rc = call.up_rebased(d_off, offsets, n + 1)) || (rc = call.sync()))) return rc;
         if (filters) {  // filter_sstables_by_key_range (range.rs:91-147) with the tables' own key ranges
             std::vector<uint8_t> bounds;
-            std::vector<uint64_t> boff(1, 0);
-            for (uint32_t i = 0; i < nsst; ++i) {
-                bounds.insert(bounds.end(), tables[i]->smallest.begin(), tables[i]->smallest.end());
-                boff.push_back(bounds.size());
-                bounds.insert(bounds.end(), tables[i]->biggest.begin(), tables[i]->biggest.end());
-                boff.push_back(bounds.size());
-            }
-            bounds.push_back(0);  // never NULL
+            std::vector<uint64_t> boff;
+            table_bounds(nsst, tables, &bounds, &boff);
             if ((rc = multi_probe(d_keys, d_off, stride, n, 1, nsst, filters, bounds.data(), boff.data(), d_cand, call.s)))
                 return rc;
         }
@@ -4891,6 +4901,258 @@ int vbf_vlog_walk_host(const vbf_vlog* v, uint64_t start, uint64_t budget, uint6
             (rc = call.down(values, o.values, p.vb)) || (rc = call.down(value_off, o.value_off, n + 1)) ||
             (rc = call.down(created_ms, o.created, n)) || (rc = call.down(tombstones, o.tomb, n)))
             return rc;
+        return call.finish();
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+}
+
+}  // extern "C"
+
+// ---- the garbage collector's handler over one chunk (GC::gc_handler) ----
+
+namespace {
+
+// The argument checks of vbf_gc_collect_host that need no HIP call and follow no handle.  A NULL
+// scalar leaves everything unwritten; otherwise the six scalars are written first.
+int gc_check(const vbf_vlog* v, uint64_t tail, uint64_t log_size, uint32_t nsst, const vbf_table* const* tables,
+             const vbf_filter* const* filters, const uint8_t* ov_keys, const uint64_t* ov_off,
+             const uint32_t* ov_val_offsets, const int64_t* ov_created_ms, const uint8_t* ov_tombstones, uint64_t ov_n,
+             uint64_t* n_chunk, uint64_t* n_invalid, uint64_t* n_puts, uint64_t* append_len, uint64_t* end_off,
+             int* stop) {
+    if (!n_chunk) return fail(VBF_EINVAL, "n_chunk is NULL");
+    if (!n_invalid) return fail(VBF_EINVAL, "n_invalid is NULL");
+    if (!n_puts) return fail(VBF_EINVAL, "n_puts is NULL");
+    if (!append_len) return fail(VBF_EINVAL, "append_len is NULL");
+    if (!end_off) return fail(VBF_EINVAL, "end_off is NULL");
+    if (!stop) return fail(VBF_EINVAL, "stop is NULL");
+    *n_chunk = *n_invalid = *n_puts = *append_len = 0;
+    *end_off = tail;
+    *stop = VBF_WALK_END;
+    if (!v) return fail(VBF_EINVAL, "vlog is NULL");
+    if (nsst && !tables) return fail(VBF_EINVAL, "tables is NULL");
+    for (uint32_t i = 0; i < nsst; ++i)
+        if (!tables[i]) return fail(VBF_EINVAL, "tables[%u] is NULL", i);
+    if (filters)
+        for (uint32_t i = 0; i < nsst; ++i)
+            if (!filters[i]) return fail(VBF_EINVAL, "filters[%u] is NULL", i);
+    if (ov_n) {
+        if (!ov_keys) return fail(VBF_EINVAL, "ov_keys is NULL");
+        if (!ov_off) return fail(VBF_EINVAL, "ov_off is NULL");
+        if (!ov_val_offsets) return fail(VBF_EINVAL, "ov_val_offsets is NULL");
+        if (!ov_created_ms) return fail(VBF_EINVAL, "ov_created_ms is NULL");
+        if (!ov_tombstones) return fail(VBF_EINVAL, "ov_tombstones is NULL");
+        if (ov_n > 0x7FFFFFFEull)
+            return fail(VBF_EINVAL, "too many overlay keys: %llu (limit 2^31 - 2)", (unsigned long long)ov_n);
+        for (uint64_t k = 0; k < ov_n; ++k)
+            if (ov_off[k] > ov_off[k + 1]) return fail(VBF_EINVAL, "ov_off descends at key %llu", (unsigned long long)k);
+        for (uint64_t k = 0; k + 1 < ov_n; ++k)
+            if (cmp_host(ov_keys + ov_off[k], ov_off[k + 1] - ov_off[k], ov_keys + ov_off[k + 1],
+                         ov_off[k + 2] - ov_off[k + 1]) >= 0)
+                return fail(VBF_EINVAL, "overlay keys not strictly ascending at key %llu", (unsigned long long)(k + 1));
+    }
+    // the `tail` entry is 29 bytes: from here on no entry could follow it below 2^32
+    if (log_size + 25 > kVlogMaxOffset || log_size + 25 < log_size)
+        return fail(VBF_EINVAL, "log_size %llu: an appended entry would start at or beyond 2^32, where data.db's u32 "
+                    "value offset cannot address it", (unsigned long long)log_size);
+    return VBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbf_gc_collect_host(const vbf_vlog* v, uint64_t tail, uint64_t chunk_bytes, uint64_t log_size, int64_t now_ms,
+                        uint32_t nsst, const vbf_table* const* tables, const vbf_filter* const* filters,
+                        const uint8_t* ov_keys, const uint64_t* ov_off, const uint32_t* ov_val_offsets,
+                        const int64_t* ov_created_ms, const uint8_t* ov_tombstones, uint64_t ov_n, uint8_t* verdict,
+                        uint64_t entries_cap, uint8_t* append, uint64_t append_cap, uint32_t* put_ids,
+                        uint32_t* put_val_offsets, uint8_t* put_tombstones, uint64_t puts_cap, uint64_t* n_chunk,
+                        uint64_t* n_invalid, uint64_t* n_puts, uint64_t* append_len, uint64_t* end_off, int* stop) {
+    int rc = gc_check(v, tail, log_size, nsst, tables, filters, ov_keys, ov_off, ov_val_offsets, ov_created_ms,
+                      ov_tombstones, ov_n, n_chunk, n_invalid, n_puts, append_len, end_off, stop);
+    if (rc) return rc;
+    if (tail < v->base || tail - v->base > v->len)
+        return fail(VBF_EINVAL, "tail %llu outside the window [%llu, %llu]", (unsigned long long)tail,
+                    (unsigned long long)v->base, (unsigned long long)(v->base + v->len));
+    const int device = v->device;
+    for (uint32_t i = 0; i < nsst; ++i)
+        if (tables[i]->device != device)
+            return fail(VBF_EINVAL, "tables[%u] lives on device %d, the log on %d", i, tables[i]->device, device);
+    if (!nsst) filters = nullptr;
+    if (tail - v->base == v->len) return ok();  // nothing to walk: no device work
+    try {
+        // Lock order as in vbf_table_get_host: the filters' locks and their drain, then the device.
+        MultiLock lk(filters, filters ? nsst : 0);
+        if ((rc = lk.drain())) return rc;
+        if (filters)
+            for (uint32_t i = 0; i < nsst; ++i)
+                if (filters[i]->bits->device != device)
+                    return fail(VBF_EINVAL, "filters[%u] lives on device %d, the log on %d", i,
+                                filters[i]->bits->device, device);
+        HOST_CALL(call, device);
+        hipStream_t s = call.s;
+        WalkPlan p;
+        if ((rc = walk_sweep(v, tail, chunk_bytes, s, &p))) return rc;
+        const uint64_t n = p.n;
+        *n_chunk = n;
+        *end_off = v->base + p.end_rel;
+        *stop = p.stop;
+        if (n > 0x7FFFFFFEull)
+            return fail(VBF_EINVAL, "too many entries: %llu (limit 2^31 - 2)", (unsigned long long)n);
+        if (!n) return call.finish();  // a torn first entry: nothing to judge
+        const uint64_t ok0 = ov_n ? ov_off[0] : 0, okb = ov_n ? ov_off[ov_n] - ok0 : 0;
+        size_t scan_b = 0, sel_b = 0;
+        HIP_TRY(vbf::scan_u64(nullptr, &scan_b, nullptr, nullptr, n + 2, s));
+        HIP_TRY(vbf::select_u32(nullptr, &sel_b, nullptr, nullptr, nullptr, nullptr, n, s));
+        // the chunk (entry_off | keys | key_off | created), the lookup (cand | found | val_off | wcreated),
+        // the overlay, the judge's arrays: 79 bytes per chunk entry plus its key, nsst with filters
+        DevImage img;
+        const auto p_eo = img.add<uint64_t>(n + 1);
+        const auto p_keys = img.add<uint8_t>(p.kb + 1);
+        const auto p_ko = img.add<uint64_t>(n + 1);
+        const auto p_cand = img.add<uint8_t>(n * nsst, filters);
+        const auto p_found = img.add<uint8_t>(n);
+        const auto p_val = img.add<uint32_t>(n);
+        const auto p_wcr = img.add<uint64_t>(n);
+        const auto p_okeys = img.add<uint8_t>(okb + 1, ov_n);
+        const auto p_ooff = img.add<uint64_t>(ov_n + 1, ov_n);
+        const auto p_oval = img.add<uint32_t>(ov_n, ov_n);
+        const auto p_ocr = img.add<int64_t>(ov_n, ov_n);
+        const auto p_otb = img.add<uint8_t>(ov_n, ov_n);
+        const auto p_verdict = img.add<uint8_t>(n);
+        const auto p_keep = img.add<uint8_t>(n);
+        const auto p_ids = img.add<uint32_t>(n);
+        const auto p_size = img.add<uint64_t>(n + 2);
+        const auto p_pos = img.add<uint64_t>(n + 2);
+        const auto p_ksrc = img.add<uint64_t>(n);
+        const auto p_vsrc = img.add<uint64_t>(n);
+        const auto p_klen = img.add<uint32_t>(n);
+        const auto p_vlen = img.add<uint32_t>(n);
+        const auto p_pids = img.add<uint32_t>(n + 1);
+        const auto p_misc = img.add<uint64_t>(1);
+        const auto p_res = img.add<vbf::GcRes>(1);
+        const auto p_tmp = img.add<uint8_t>(std::max(scan_b, sel_b));
+        if ((rc = img.alloc(call, kWsGc))) return rc;
+        vbf::WalkOut o{};
+        o.entry_off = img.ptr(p_eo);
+        o.keys = img.ptr(p_keys);
+        o.key_off = img.ptr(p_ko);
+        if ((rc = walk_fill(&p, o, s))) return rc;
+        if ((rc = call.up(img.ptr(p_okeys), ov_n && okb ? ov_keys + ok0 : nullptr, okb)) ||
+            (rc = call.up_rebased(img.ptr(p_ooff), ov_off, ov_n ? ov_n + 1 : 0)) ||
+            (rc = call.up(img.ptr(p_oval), ov_val_offsets, ov_n)) || (rc = call.up(img.ptr(p_ocr), ov_created_ms, ov_n)) ||
+            (rc = call.up(img.ptr(p_otb), ov_tombstones, ov_n)))
+            return rc;
+        if (nsst) {  // step 3 of GC::get, exactly vbf_table_get_host's device side
+            if (filters) {
+                std::vector<uint8_t> bounds;
+                std::vector<uint64_t> boff;
+                table_bounds(nsst, tables, &bounds, &boff);
+                if ((rc = multi_probe(o.keys, o.key_off, 0, n, 1, nsst, filters, bounds.data(), boff.data(),
+                                      img.ptr(p_cand), s)))
+                    return rc;
+            }
+            if ((rc = table_lookup(o.keys, o.key_off, 0, n, nsst, tables, img.ptr(p_cand), img.ptr(p_found), nullptr,
+                                   img.ptr(p_val), img.ptr(p_wcr), s)))
+                return rc;
+        } else {
+            HIP_TRY(hipMemsetAsync(img.ptr(p_found), 0, n, s));
+        }
+        vbf::GcArgs a{};
+        a.bytes = v->bytes;
+        a.len = v->len;
+        a.base = v->base;
+        a.n = n;
+        a.entry_off = o.entry_off;
+        a.ov_keys = img.ptr(p_okeys);
+        a.ov_off = img.ptr(p_ooff);
+        a.ov_val = img.ptr(p_oval);
+        a.ov_created = img.ptr(p_ocr);
+        a.ov_tomb = img.ptr(p_otb);
+        a.ov_n = ov_n;
+        a.found = img.ptr(p_found);
+        a.val_off = img.ptr(p_val);
+        a.wcreated = img.ptr(p_wcr);
+        a.verdict = img.ptr(p_verdict);
+        a.keep = img.ptr(p_keep);
+        a.ids = img.ptr(p_ids);
+        a.size = img.ptr(p_size);
+        a.pos = img.ptr(p_pos);
+        a.ksrc = img.ptr(p_ksrc);
+        a.vsrc = img.ptr(p_vsrc);
+        a.klen = img.ptr(p_klen);
+        a.vlen = img.ptr(p_vlen);
+        a.put_ids = img.ptr(p_pids);
+        a.res = img.ptr(p_res);
+        vbf::GcRes res{};
+        uint64_t total = 0;
+        HIP_TRY(hipMemsetAsync(a.res, 0, sizeof(vbf::GcRes), s));
+        HIP_TRY(hipMemsetAsync(&a.res->bad, 0xFF, 8, s));
+        HIP_TRY(hipMemsetAsync(img.ptr(p_pids), 0xFF, 4, s));  // put 0 comes from no chunk entry
+        vbf::phase_begin(vbf::kPhaseGcJudge, s);
+        HIP_TRY(vbf::gc_overlay(a, s));
+        HIP_TRY(vbf::gc_judge(a, s));
+        size_t tb = scan_b;
+        HIP_TRY(vbf::scan_u64(img.ptr(p_tmp), &tb, a.size, img.ptr(p_pos), n + 2, s));
+        tb = sel_b;
+        HIP_TRY(vbf::select_u32(img.ptr(p_tmp), &tb, a.ids, a.keep, img.ptr(p_pids) + 1, img.ptr(p_misc), n, s));
+        vbf::phase_end(vbf::kPhaseGcJudge, s);
+        // the one readback: the invalid count, the first BAD entry, the last valid one, the byte total
+        if ((rc = call.down(&res, a.res, 1)) || (rc = call.down(&total, a.pos + n + 1, 1)) || (rc = call.sync()))
+            return rc;
+        if (res.bad != ~0ull) {
+            uint32_t at = 0;
+            if ((rc = call.down(&at, a.val_off + res.bad, 1)) || (rc = call.sync())) return rc;
+            return fail(VBF_EINVAL, "gc: the most recent entry of chunk entry %llu, at %u, is not a whole entry of the log",
+                        (unsigned long long)res.bad, at);
+        }
+        *n_invalid = res.n_invalid;
+        const uint64_t np = res.n_invalid ? 1 + n - res.n_invalid : 0;  // nothing to collect (:228-230): no put
+        if (!np) total = 0;
+        *n_puts = np;
+        *append_len = total;
+        if (verdict && entries_cap < n)
+            return fail(VBF_EINVAL, "entries_cap %llu < %llu entries", (unsigned long long)entries_cap,
+                        (unsigned long long)n);
+        if (!np) {
+            if ((rc = call.down(verdict, a.verdict, n))) return rc;
+            return call.finish();
+        }
+        if (log_size + total >= kVlogMaxOffset && res.last_valid) {  // only then can an entry start at 2^32 or beyond
+            uint64_t last = 0;
+            if ((rc = call.down(&last, a.pos + res.last_valid, 1)) || (rc = call.sync())) return rc;
+            if (log_size + last >= kVlogMaxOffset)
+                return fail(VBF_EINVAL, "the last entry would start at %llu, at or beyond 2^32: data.db's u32 value offset "
+                            "cannot address it", (unsigned long long)(log_size + last));
+        }
+        if ((put_ids || put_val_offsets || put_tombstones) && puts_cap < np)
+            return fail(VBF_EINVAL, "puts_cap %llu < %llu puts", (unsigned long long)puts_cap, (unsigned long long)np);
+        if (append && append_cap < total)
+            return fail(VBF_EINVAL, "append_cap %llu < %llu log bytes", (unsigned long long)append_cap,
+                        (unsigned long long)total);
+        if ((rc = call.down(verdict, a.verdict, n)) || (rc = call.down(put_ids, a.put_ids, np))) return rc;
+        if (append || put_val_offsets || put_tombstones) {
+            DevImage out;  // append | put_val_offsets | put_tombstones: 1 byte per appended byte, 5 per put
+            const auto p_app = out.add<uint8_t>(total, append);
+            const auto p_pvo = out.add<uint32_t>(np, put_val_offsets);
+            const auto p_ptb = out.add<uint8_t>(np, put_tombstones);
+            if ((rc = out.alloc(call, kWsGcOut))) return rc;
+            a.n_puts = np;
+            a.total = total;
+            a.log_size = log_size;
+            a.new_tail = *end_off;
+            a.now_ms = now_ms;
+            a.append = out.ptr(p_app);
+            a.put_val_offsets = out.ptr(p_pvo);
+            a.put_tombstones = out.ptr(p_ptb);
+            vbf::phase_begin(vbf::kPhaseGcEmit, s);
+            HIP_TRY(vbf::gc_emit(a, s));
+            vbf::phase_end(vbf::kPhaseGcEmit, s);
+            if ((rc = call.down(append, a.append, total)) || (rc = call.down(put_val_offsets, a.put_val_offsets, np)) ||
+                (rc = call.down(put_tombstones, a.put_tombstones, np)))
+                return rc;
+        }
         return call.finish();
     } catch (const std::bad_alloc&) {
         return table_no_memory();

@@ -34,7 +34,7 @@ enum Phase { kPhaseTileSort = 0, kPhaseTranspose = 1, kPhaseSegOr = 2, kPhaseAto
              kPhaseEncIndex = 16, kPhaseEncData = 17, kPhaseTableOpen = 18, kPhaseTableGet = 19,
              kPhaseScanRank = 20, kPhaseScanEmit = 21, kPhaseVlogSizes = 22, kPhaseVlogCopy = 23,
              kPhaseVlogEncode = 24, kPhaseMemSort = 25, kPhaseMemMerge = 26, kPhaseFilterInsert = 27,
-             kNumPhases = 28 };
+             kPhaseGcJudge = 28, kPhaseGcEmit = 29, kNumPhases = 30 };
 void phase_begin(int phase, hipStream_t s);
 void phase_end(int phase, hipStream_t s);
 
@@ -317,6 +317,54 @@ struct WalkOut {           // the caller's arrays (each may be NULL) and the seg
 hipError_t walk_passes(const WalkArgs& a, void* scan_tmp, size_t scan_bytes, hipStream_t s);
 hipError_t walk_emit(const WalkArgs& a, const WalkOut& o, hipStream_t s);
 hipError_t walk_tail(const WalkOut& o, uint64_t n, uint64_t end_off, uint64_t kb, uint64_t vb, hipStream_t s);
+// The GC's data step (vbf_gc.hip): every entry of a walked chunk judged against its most recent
+// entry, then the `tail` entry and the surviving entries written from the window into the bytes to
+// append.  Per chunk entry i: its file position, and the lookup's answer (found / val_off / wcreated:
+// vbf_table_get_*'s arrays, which the overlay pass overrides where the overlay holds the key).
+enum : uint8_t { kGcValid = 0, kGcAbsent = 1, kGcDeleted = 2, kGcLogNone = 3, kGcLogTombstone = 4, kGcOlder = 5,
+                 kGcStar = 6, kGcBad = 0xFF };
+constexpr uint32_t kGcNoEntry = 0xFFFFFFFFu;  // put_ids[0]: the `tail` put comes from no chunk entry
+constexpr uint64_t kGcTailSize = 17 + 4 + 8;  // the `tail` entry: header, "tail", LE64(new tail)
+struct GcRes {               // read back by the host after the judge
+    uint64_t n_invalid;
+    uint64_t bad;            // the first chunk entry whose most recent entry is BAD, ~0: none
+    uint64_t last_valid;     // 1 + the last valid chunk entry, 0: none
+};
+struct GcArgs {
+    const uint8_t* bytes;    // the log's bytes [base, base + len)
+    uint64_t len, base;
+    uint64_t n;              // chunk entries
+    const uint64_t* entry_off;   // [n] file positions (the walk's)
+    const uint8_t* ov_keys;      // the overlay: ov_n strictly ascending keys, key k = ov_keys[ov_off[k] .. ov_off[k+1])
+    const uint64_t* ov_off;
+    const uint32_t* ov_val;
+    const int64_t* ov_created;
+    const uint8_t* ov_tomb;
+    uint64_t ov_n;
+    uint8_t* found;          // [n] 0 nowhere, 1 live, 2 tombstone
+    uint32_t* val_off;       // [n] the winner's file position
+    uint64_t* wcreated;      // [n] the winner's created_at
+    uint8_t* verdict;        // [n] kGc* (judge)
+    uint8_t* keep;           // [n] 1 for a valid entry
+    uint32_t* ids;           // [n] i, the select's input
+    uint64_t* size;          // [n + 2] bytes appended for item 0 (the `tail` put) and for entry i at [i + 1]; [n + 1] = 0
+    uint64_t* ksrc;          // [n] valid entries: window positions of the own key and of the most recent value
+    uint64_t* vsrc;
+    uint32_t* klen;          // [n] and their lengths
+    uint32_t* vlen;
+    GcRes* res;
+    const uint64_t* pos;     // [n + 2] exclusive scan of size; [n + 1] = the bytes appended
+    const uint32_t* put_ids; // [n_puts] put j's chunk entry, kGcNoEntry for put 0 (the select's output behind it)
+    uint64_t n_puts, total;
+    uint64_t log_size, new_tail;
+    int64_t now_ms;
+    uint8_t* append;         // emit's outputs
+    uint32_t* put_val_offsets;
+    uint8_t* put_tombstones;
+};
+hipError_t gc_overlay(const GcArgs& a, hipStream_t s);
+hipError_t gc_judge(const GcArgs& a, hipStream_t s);
+hipError_t gc_emit(const GcArgs& a, hipStream_t s);
 // Batched probe across SSTs (vbf_multi.hip).
 struct MultiSst {
     const uint32_t* words;

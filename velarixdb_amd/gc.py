@@ -10,6 +10,11 @@ GC table (:245-251, GC::put :404-419).  Here:
       ValueLog.read_chunk (vbf_vlog_walk_*), then Table.get_many over `tables` (step 3 of GC::get),
       then ValueLog.get_many for the most recent values, then ValueLog.encode for the bytes to append.
 
+  collect_device(...same arguments...) -> GcResult or None
+      the same in one device pass (vbf_gc_collect_host): the log window and the tables are already on
+      the device, so no key or value crosses to the host between the steps; adds GcResult.verdict.
+      collect stays the default route and the baseline of tools/gc_collect_bench.py.
+
 `overlay` maps a key to (val_offset, created_ms, tombstone): what steps 1 and 2 of GC::get found in
 the GC memtable and the read-only memtables.  The caller folds those two steps (the active table
 first, else the most recent of the read-only ones); a key found there skips the tables.
@@ -26,12 +31,14 @@ so their order in its log is not fixed.  Here they keep the chunk's order.
 Out of scope: hole punching, fsync, the memtables themselves, timers.  The per-entry flags are
 plain numpy on arrays that are already on the host.
 """
+import ctypes
 import struct
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import table as _table
+from ._lib import VBF_EINVAL, VBF_GC_VALID, VbfError, call, lib
 from .vlog import BAD, KEY_MISMATCH, VALUE, ValueLog
 
 TOMB_STONE_MARKER = b"*"
@@ -48,6 +55,7 @@ class GcResult:
     put_val_offsets: np.ndarray   # uint32: each appended entry's position
     put_created_ms: np.ndarray    # int64: now_ms
     put_tombstones: np.ndarray    # uint8: 1 where the value is empty (:411)
+    verdict: np.ndarray = None    # uint8 per chunk entry, VBF_GC_* (collect_device only)
 
 
 def collect(vlog, tables, tail, chunk_bytes, log_size, now_ms, filters=None, overlay=None):
@@ -89,3 +97,56 @@ def collect(vlog, tables, tail, chunk_bytes, log_size, now_ms, filters=None, ove
     append, offs = ValueLog.encode(put_keys, values, created_ms=created, base=log_size, device=vlog.device)
     tomb = np.array([len(v) == 0 for v in values], np.uint8)
     return GcResult(np.flatnonzero(invalid).astype(np.uint64), total, new_tail, append, put_keys, offs, created, tomb)
+
+
+def _pack_overlay(overlay):
+    """The overlay dict as vbf_gc_collect_host takes it: sorted keys back to back (never NULL), their
+    n + 1 offsets, val_offsets, created_ms, tombstones."""
+    items = sorted((bytes(k), v) for k, v in (overlay or {}).items())
+    keys = np.frombuffer(b"".join(k for k, _ in items) + b"\0", np.uint8)
+    off = np.concatenate([[0], np.cumsum([len(k) for k, _ in items])]).astype(np.uint64)
+    vo = np.array([int(v[0]) for _, v in items], np.uint32)
+    cr = np.array([int(v[1]) for _, v in items], np.int64)
+    tb = np.array([1 if v[2] else 0 for _, v in items], np.uint8)
+    return len(items), keys, off, vo, cr, tb
+
+
+def collect_device(vlog, tables, tail, chunk_bytes, log_size, now_ms, filters=None, overlay=None):
+    """collect() in one device pass (C ABI vbf_gc_collect_host, velarixdb_amd/csrc/vbf_gc.hip): the walk,
+    the lookups, the verdicts and the bytes to append without a key or a value crossing to the host in
+    between.  The same arguments and the same GcResult (or None), plus `verdict`, the VBF_GC_* reason
+    per chunk entry; with nothing to collect the verdicts are still computed but None is returned.
+    One size query, then one filling call.  Raises ValueError when a most recent entry is BAD."""
+    tail, chunk_bytes, log_size, now_ms = int(tail), int(chunk_bytes), int(log_size), int(now_ms)
+    tables = list(tables)
+    nsst = len(tables)
+    if filters is not None:
+        filters = list(filters)
+        if len(filters) != nsst:
+            raise ValueError("one filter per table")
+    th = (ctypes.c_void_p * max(nsst, 1))(*[t._h.value for t in tables])
+    fh = (ctypes.c_void_p * max(nsst, 1))(*[f._h.value for f in filters]) if filters is not None else None
+    ov_n, ok, oo, ovo, ocr, otb = _pack_overlay(overlay)
+    vp = lambda x: x.ctypes.data if x.size else None
+    head = (vlog._h, tail, chunk_bytes, log_size, now_ms, nsst, th, fh)
+    head += (ok.ctypes.data, oo.ctypes.data, vp(ovo), vp(ocr), vp(otb), ov_n) if ov_n else (None, None, None, None, None, 0)
+    sc = [ctypes.c_uint64() for _ in range(5)]
+    stop = ctypes.c_int()
+    scalars = [ctypes.byref(x) for x in sc] + [ctypes.byref(stop)]
+    try:
+        call("vbf_gc_collect_host", *head, None, 0, None, 0, None, None, None, 0, *scalars)
+        n, n_invalid, n_puts, alen, end_off = (x.value for x in sc)
+        if not n_invalid:
+            return None
+        verdict, append = np.zeros(n, np.uint8), np.zeros(alen, np.uint8)
+        ids, offs, tomb = np.zeros(n_puts, np.uint32), np.zeros(n_puts, np.uint32), np.zeros(n_puts, np.uint8)
+        call("vbf_gc_collect_host", *head, vp(verdict), n, vp(append), alen, vp(ids), vp(offs), vp(tomb), n_puts, *scalars)
+    except VbfError as e:
+        if e.code == VBF_EINVAL:
+            raise ValueError(lib.vbf_last_error().decode(errors="replace")) from None
+        raise
+    at = offs.astype(np.int64) - log_size  # put j's key: 17 bytes into its entry, its length in the first 4
+    klen = np.ascontiguousarray(append[at[:, None] + np.arange(4)]).view("<u4").ravel()
+    put_keys = [append[a + 17:a + 17 + kl].tobytes() for a, kl in zip(at.tolist(), klen.tolist())]
+    return GcResult(np.flatnonzero(verdict != VBF_GC_VALID).astype(np.uint64), end_off - tail, end_off, append.tobytes(),
+                    put_keys, offs, np.full(n_puts, now_ms, np.int64), tomb, verdict)
