@@ -55,6 +55,11 @@
  *   write_valid_entries_to_vlog        src/gc/garbage_collector.rs:304-317 -> vbf_gc_collect_host (the rest of `append`)
  *   GC::put                            src/gc/garbage_collector.rs:404-419 -> vbf_gc_collect_host (put_val_offsets,
  *                                                                             put_tombstones)
+ *   MemTable (an immutable one)        src/memtable/mem.rs:207-221 -> vbf_memtable_open_* (a batch of inserts)
+ *   MemTable::get                      src/memtable/mem.rs:223-230 -> vbf_memtable_get_* (per layer)
+ *   DataStore::search_gc_entries       src/db/store.rs:489-501     -> vbf_memtable_get_* (the gc layer)
+ *   DataStore::get                     src/db/store.rs:442-481     -> vbf_memtable_get_* (steps 0-2),
+ *                                                                     vbf_store_get_host (the whole get)
  *
  * Key batches.  `keys` holds the key bytes back to back.  When `offsets` is non-NULL it has
  * n+1 nondecreasing entries and key j is keys[offsets[j] .. offsets[j+1]) (positions are
@@ -70,13 +75,14 @@
  * Threads.  Every `_host` entry point and every call on a handle (vbf_filter_*, vbf_table_*,
  * vbf_vlog_*) may be made from any number of threads at once, on the same or on different devices,
  * with the answers a single caller gets.  Calls on one filter are ordered by the filter's lock, as
- * the reference's Mutex<BitVec> orders them; a vbf_table and a vbf_vlog are immutable once opened,
+ * the reference's Mutex<BitVec> orders them; a vbf_table, a vbf_vlog and a vbf_memtable are immutable once opened,
  * so any number of gets and scans may read them together.  Per device the library serialises what
  * shares its staging: vbf_build_host, vbf_probe_host and the filters' set_host / contains_host /
  * words copies take turns on the device's two staging streams, and the other `_host` entry points
  * (sst_decode, sst_encode, rebuild_from_sst, multi_probe, compact_merge, compact_write,
  * table_open, table_get, table_scan, vlog_open, vlog_get, vlog_encode, vlog_walk, memtable_sort,
- * flush_write, gc_collect, and filter_insert_host on a device-resident filter) take turns on its shared
+ * flush_write, gc_collect, memtable_open, memtable_export, memtable_encode, memtable_get, store_get,
+ * and filter_insert_host on a device-resident filter) take turns on its shared
  * stream, each from its first upload to its last download; the two groups overlap each other, and
  * devices never wait for each other.  A call that spans several devices (vbf_multi_probe_host over filters on several GPUs)
  * holds one device at a time.  Locks are taken filters first (in address order), then the device.
@@ -121,7 +127,7 @@ int vbf_device_count(int* count);
  * emit + key copy, 22 value-log fetch sizes + scan, 23 value-log fetch copy, 24 value-log encode
  * (its check and its copy), 25 memtable tile sort (with its prefix pass), 26 memtable merge levels
  * + keep flags + select, 27 filter insert (count passes and the build), 28 GC judge (with its overlay
- * search, scan and select), 29 GC emit.
+ * search, scan and select), 29 GC emit, 30 memtable get.
  * vbf_profile_read synchronizes, returns per-phase summed ms and launch counts, and resets; it
  * fills the first `nphases` phases, so a caller built against a shorter list keeps working (the
  * later phases' records are dropped). */
@@ -993,6 +999,124 @@ int vbf_gc_collect_host(const vbf_vlog* v, uint64_t tail, uint64_t chunk_bytes, 
                         uint32_t* put_ids, uint32_t* put_val_offsets, uint8_t* put_tombstones, uint64_t puts_cap,
                         uint64_t* n_chunk, uint64_t* n_invalid, uint64_t* n_puts, uint64_t* append_len,
                         uint64_t* end_off, int* stop);
+
+/* ---- device-resident memtables and the whole get ----
+ * DataStore::get (src/db/store.rs:442-481) asks four places in order -- the GC's not-yet-synced
+ * entries (search_gc_entries, :489-501), the active memtable (:452-456), the read-only memtables
+ * (:458-472), the SSTs (:474-478) -- and then reads the value log (get_value_from_vlog, :628-641).
+ * vbf_table_get_* and vbf_vlog_get_* are the last two; these entry points are the first three and
+ * the join of all five.
+ *
+ * A vbf_memtable is an immutable memtable on a device: the outcome of MemTable::insert
+ * (memtable/mem.rs:207-221) for a batch of puts in arrival order, i.e. vbf_memtable_sort (the last
+ * put of a key wins) and the gather of the survivors.  The handle owns the sorted keys, their
+ * offsets, the three per-entry arrays and the lookup's side table (pfx: every key's first 8 bytes as
+ * a big-endian word, zero-padded; 8 bytes per entry).  A mutable memtable is a sequence of such
+ * handles: a caller that keeps putting opens the active table again from its puts.
+ * open_*: vbf_flush_write_host's input convention -- val_offsets (u32) / created_ms (i64) /
+ * tombstones may each be NULL and then mean zeros; a tombstone byte != 0 is a tombstone, as the
+ * encoder writes it.  n == 0 opens an empty memtable (no device work).  n > 2^31 - 1 and descending
+ * offsets are VBF_EINVAL, as in the sort.  _dev (device arrays, the current device) copies: the
+ * gather writes new arrays anyway, so the caller's may go once it returns; it synchronises `stream`
+ * for the sort's count (the key bytes' extent rides along), for the gathered key bytes, and once at
+ * its end, so the handle is complete on return and any stream may read it.  _host uploads to
+ * `device`; synchronous. */
+typedef struct vbf_memtable vbf_memtable;
+int vbf_memtable_open_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                           const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones,
+                           int device, vbf_memtable** out);
+int vbf_memtable_open_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                          const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones,
+                          void* stream, vbf_memtable** out);
+void vbf_memtable_free(vbf_memtable* t);
+uint64_t vbf_memtable_entries(const vbf_memtable* t);   /* distinct keys */
+uint64_t vbf_memtable_key_bytes(const vbf_memtable* t); /* their bytes, back to back */
+int vbf_memtable_device(const vbf_memtable* t);
+/* The sorted entries, in host memory: key e = keys[key_off[e] .. key_off[e+1]), key_off has
+ * entries + 1 positions from 0 (so entries_cap + 1 slots).  Exactly the layout of
+ * vbf_gc_collect_host's overlay arrays; key 0 and the last key are the summary's two keys
+ * (table.rs:270-274).  Every array may be NULL; all of them NULL is the size query through the
+ * accessors above.  A capacity that is too small (keys_cap < key bytes with keys given, entries_cap
+ * < entries with a per-entry array given) is VBF_EINVAL with nothing written. */
+int vbf_memtable_export_host(const vbf_memtable* t, uint8_t* keys, uint64_t keys_cap, uint64_t* key_off,
+                             uint32_t* val_offsets, int64_t* created_ms, uint8_t* tombstones,
+                             uint64_t entries_cap);
+/* Flusher::flush (src/flush/flusher.rs:37-64) of an open memtable: vbf_sst_encode_dev over the
+ * handle's arrays, with vbf_flush_write_host's conventions -- *data_len / *index_len are always
+ * written, data / index may be NULL (a size query), a capacity that is too small is VBF_EINVAL with
+ * the sizes written and no output touched.  The bytes are those of vbf_flush_write_host over the same
+ * puts.  An empty memtable is VBF_EINVAL ("Cannot flush an empty table", flusher.rs:40-44). */
+int vbf_memtable_encode_host(const vbf_memtable* t, uint8_t* data, uint64_t data_cap, uint64_t* data_len,
+                             uint8_t* index, uint64_t index_cap, uint64_t* index_len);
+
+/* Steps 0-2 of DataStore::get for a batch of keys (layout as every entry point).  `gc` and `active`
+ * may be NULL, nro may be 0; ro[0..nro) in the reference's iteration order.  MemTable::get
+ * (memtable/mem.rs:223-230) tests its Bloom filter first; the filter has no false negatives, so a
+ * memtable lookup is the map lookup.  Per key:
+ *   gc (search_gc_entries, store.rs:489-501): a hit decides only when the entry is live AND the log
+ *     holds a live value at its offset, by vbf_vlog_get_*'s window tests on the 17-byte header in
+ *     `log`.  A tombstone entry (:494-496), a log status NONE and a log status TOMBSTONE
+ *     (get_value_from_vlog's None, :628-641) all return Ok(None) there, so the lookup FALLS THROUGH
+ *     to the active memtable (:445-447).  An offset that is BAD keeps the gc hit: the value fetch
+ *     reports BAD for that item, where the reference's get fails.  The key in the log is not
+ *     compared.  gc != NULL with log == NULL is VBF_EINVAL; without gc, log is not read.
+ *   active (:452-456): a hit decides whatever its time, found = 2 for a tombstone (:453-455), else
+ *     1.  There is no fall-through.
+ *   read-only (:458-472): a fold over ro[] in the given order from default_datetime() (time 0).  A
+ *     hit replaces the winner only when its created_at, compared as the signed 64-bit value the
+ *     memtable's DateTime holds (as vbf_gc_collect_host reads it), is strictly greater (:461); on a
+ *     tie the earlier table wins; an entry at time <= 0 never wins, and a key that only such entries
+ *     hold is not found here (found_in_table, :468, :616-618): the SSTs get their turn.
+ * found[j] is 0, 1 or 2 as in vbf_table_get_*; layer[j] is 0 for gc, 1 for active, 2 + r for
+ * read-only table r, 0xFFFFFFFF for none; val_offsets[j] and created_ms[j] (the i64's bits) are the
+ * winner's fields, 0 when not found.  Any output may be NULL.
+ * All handles live on one device (VBF_EINVAL otherwise).  n == 0 is VBF_OK with no device work; at
+ * most 2^31 - 2 keys.  Every argument check runs on the host before any HIP call.  _dev: keys and
+ * outputs on the handles' device, queued on `stream` after one synchronisation of it (the layers'
+ * descriptors' upload), as vbf_table_get_dev; with no handle at all the outputs are filled by memsets.
+ * _host: host arrays, synchronous.
+ * Kernel (csrc/vbf_memget.hip): a workgroup looks up 1024 keys, four per lane.  Per layer it stages
+ * an evenly strided sample of pfx in LDS (at most 4096 words, 32 KiB; all of pfx up to 4096
+ * entries); a lane takes its prefix's lower and upper bound in the sample, and the log2(entries /
+ * 4096) steps inside them compare pfx[mid] first and the key bytes only on a prefix tie.
+ * VBF_MEMGET=0 (environment, read per call) selects the plain kernel instead -- one binary search
+ * over the keys per layer -- with identical results.  Workspace: 56 bytes per layer. */
+int vbf_memtable_get_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                         const vbf_memtable* gc, const vbf_memtable* active, uint32_t nro,
+                         const vbf_memtable* const* ro, const vbf_vlog* log, uint8_t* found, uint32_t* layer,
+                         uint32_t* val_offsets, uint64_t* created_ms, void* stream);
+int vbf_memtable_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                          const vbf_memtable* gc, const vbf_memtable* active, uint32_t nro,
+                          const vbf_memtable* const* ro, const vbf_vlog* log, uint8_t* found, uint32_t* layer,
+                          uint32_t* val_offsets, uint64_t* created_ms);
+
+/* DataStore::get (store.rs:442-481) for a batch, from key bytes to values in one device pass: the
+ * keys go up once; vbf_memtable_get_* runs; for the keys it left undecided vbf_table_get_dev runs
+ * over `tables` (search_key_in_sstables, :579-612) -- its candidate matrix made by
+ * vbf_multi_probe_dev with the tables' own key ranges when `filters` is given, exactly as in
+ * vbf_table_get_host (filter_sstables_by_key_range, :474), and the decided keys' rows zeroed --; the
+ * two answers are merged on the device (a memtable's answer stands; otherwise the tables' stands
+ * with layer[j] = 0x80000000 | table_idx[j]); vbf_vlog_get_dev fetches the values of the merged
+ * found == 1 items, comparing the log entry's key with key j when check_keys != 0.
+ * found / layer / val_offsets / created_ms: as above after the merge; table_idx[j] is the winning
+ * table or 0xFFFFFFFF when no table answered.  status, values, values_cap, value_off and *value_bytes
+ * are vbf_vlog_get_host's, with its conventions: values == NULL is the size query (every other
+ * output is still filled), values given with values_cap < *value_bytes is VBF_EINVAL with the size
+ * written and no output array touched, n == 0 writes value_off[0] = 0.  Any output but value_bytes
+ * may be NULL.  `log` is required; gc, active, nro = 0, nsst = 0 and filters may be absent.
+ * Everything on the log's device (VBF_EINVAL otherwise); every argument check runs on the host before
+ * any HIP call.  validate_size (store.rs:443: an empty key is an error) stays with the caller: a
+ * zero-length key is an ordinary key here.  Synchronous; locks as vbf_table_get_host takes them (the
+ * filters first, then the device).  Workspace: the keys, 33 + nsst bytes per key, and the callees'.
+ * Stream synchronisations: the layers' descriptors, the tables' (and with filters the filters'
+ * table), the value bytes' total, one at the end. */
+int vbf_store_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                       const vbf_memtable* gc, const vbf_memtable* active, uint32_t nro,
+                       const vbf_memtable* const* ro, uint32_t nsst, const vbf_table* const* tables,
+                       const vbf_filter* const* filters, const vbf_vlog* log, int check_keys,
+                       uint8_t* found, uint32_t* layer, uint32_t* table_idx, uint32_t* val_offsets,
+                       uint64_t* created_ms, uint8_t* status, uint8_t* values, uint64_t values_cap,
+                       uint64_t* value_off, uint64_t* value_bytes);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ from .keys import HostBatch, I32Vec, RawMessage, Usize, pack, pack_fixed, pack_o
 from .table import GetResult, ScanResult, Table, get_many, get_values, scan_many, scan_values  # noqa: F401
 from .vlog import ValueLog, Values, Walk  # noqa: F401
 from .gc import GcResult, collect_device  # noqa: F401
-from . import compaction, gc, key_range, memtable, sst, table, vlog  # noqa: F401
+from .memtable import MemTable  # noqa: F401
+from . import compaction, gc, key_range, memtable, sst, store, table, vlog  # noqa: F401
 
 __version__ = "0.1.0"

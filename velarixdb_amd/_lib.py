@@ -168,6 +168,18 @@ SIGNATURES = {
                                     _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64),
                                     ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                     ctypes.POINTER(_u64), ctypes.POINTER(_int)]),
+    "vbf_memtable_open_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _int, ctypes.POINTER(_vp)]),
+    "vbf_memtable_open_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
+    "vbf_memtable_free": (None, [_vp]),
+    "vbf_memtable_entries": (_u64, [_vp]),
+    "vbf_memtable_key_bytes": (_u64, [_vp]),
+    "vbf_memtable_device": (_int, [_vp]),
+    "vbf_memtable_export_host": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64]),
+    "vbf_memtable_encode_host": (_int, [_vp, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, ctypes.POINTER(_u64)]),
+    "vbf_memtable_get_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vbf_memtable_get_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vbf_store_get_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _int, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64)]),
 }
 
 
@@ -221,7 +233,7 @@ def device_count():
 PHASES = ("tile_sort", "transpose", "seg_or", "atomic_build", "probe", "sst_walk", "sst_scan", "sst_emit",
           "merge_levels", "fold", "select", "probe_pack", "probe_seg", "probe_out", "enc_tile", "enc_scan",
           "enc_index", "enc_data", "table_open", "table_get", "scan_rank", "scan_emit", "vlog_sizes", "vlog_copy",
-          "vlog_encode", "mem_sort", "mem_merge", "filter_insert", "gc_judge", "gc_emit")
+          "vlog_encode", "mem_sort", "mem_merge", "filter_insert", "gc_judge", "gc_emit", "mem_get")
 
 
 def profile_read():

@@ -183,6 +183,10 @@ enum WsSlot {
     kWsVlogWalkOut = 32,
     kWsGc = 33,
     kWsGcOut = 34,
+    kWsMemOpen = 35,
+    kWsMemGetDesc = 36,
+    kWsMemGetIO = 37,
+    kWsStoreIO = 38,
 };
 struct Workspace {
     int device;
@@ -5151,6 +5155,436 @@ int vbf_gc_collect_host(const vbf_vlog* v, uint64_t tail, uint64_t chunk_bytes, 
             vbf::phase_end(vbf::kPhaseGcEmit, s);
             if ((rc = call.down(append, a.append, total)) || (rc = call.down(put_val_offsets, a.put_val_offsets, np)) ||
                 (rc = call.down(put_tombstones, a.put_tombstones, np)))
+                return rc;
+        }
+        return call.finish();
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+}
+
+}  // extern "C"
+
+// ---- device-resident memtables and the whole get (DataStore::get, src/db/store.rs:442-501) ----
+
+// A memtable as the sort and the gather leave it: the distinct keys ascending with their offsets, the
+// three per-entry arrays and the lookup's prefix table, in one allocation.  Immutable once opened.
+struct vbf_memtable {
+    int device = 0;
+    uint64_t n = 0, key_bytes = 0;
+    void* mem = nullptr;  // keys | off | pfx | val | created | tomb
+    vbf::MemDesc desc{};
+    ~vbf_memtable() {
+        if (!mem || hip_forked()) return;  // a forked child: the parent's allocation
+        int prev = -1;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(device);
+        (void)hipFree(mem);
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+namespace {
+
+int memtable_open_check(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, vbf_memtable** out) {
+    if (!out) return fail(VBF_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (n > 0x7FFFFFFFull) return fail(VBF_EINVAL, "too many entries (%llu > 2^31 - 1)", (unsigned long long)n);
+    return check_keys(keys, offsets, stride, n);
+}
+
+// The puts (device pointers, n in [1, 2^31); ends = the first and the last offset, which may still be
+// on their way from the device until the sort has synchronised) sorted and gathered into the handle on
+// the current device.  Two stream synchronisations: the sort's count, the gathered key bytes.
+int memtable_fill(vbf_memtable& t, const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                  const uint64_t* ends, const uint32_t* val, const int64_t* created, const uint8_t* tomb, hipStream_t s) {
+    void* ws = nullptr;
+    int rc = get_workspace(s, n * 4, &ws, kWsMemOpen);
+    if (rc) return rc;
+    uint32_t* ids = static_cast<uint32_t*>(ws);
+    uint64_t nd = 0;
+    const uint64_t* soff = nullptr;
+    if ((rc = memtable_sort(keys, offsets, stride, n, ids, &nd, &soff, s))) return rc;
+    const uint64_t kb = ends[1] - ends[0];  // read back by the sort's synchronisation; ascending: the sort passed
+    DevImage img;
+    const auto p_keys = img.add<uint8_t>(kb + 1);
+    const auto p_off = img.add<uint64_t>(nd + 1);
+    const auto p_pfx = img.add<uint64_t>(nd);
+    const auto p_val = img.add<uint32_t>(nd);
+    const auto p_cr = img.add<int64_t>(nd);
+    const auto p_tb = img.add<uint8_t>(nd);
+    HIP_TRY(hipMalloc(&t.mem, img.bytes));
+    img.base = t.mem;
+    // an absent per-entry array means zeros
+    if (!val) HIP_TRY(hipMemsetAsync(img.ptr(p_val), 0, nd * 4, s));
+    if (!created) HIP_TRY(hipMemsetAsync(img.ptr(p_cr), 0, nd * 8, s));
+    if (!tomb) HIP_TRY(hipMemsetAsync(img.ptr(p_tb), 0, nd, s));
+    uint64_t gkb = 0;
+    if ((rc = gather_entries(keys, soff, created, tomb, val, ids, nd, img.ptr(p_keys), kb, img.ptr(p_off),
+                             created ? img.ptr(p_cr) : nullptr, tomb ? img.ptr(p_tb) : nullptr,
+                             val ? img.ptr(p_val) : nullptr, &gkb, s)))
+        return rc;
+    HIP_TRY(vbf::mem_prefixes(img.ptr(p_keys), img.ptr(p_off), nd, img.ptr(p_pfx), s));
+    t.n = nd;
+    t.key_bytes = gkb;
+    t.desc = vbf::MemDesc{img.ptr(p_keys), img.ptr(p_off), img.ptr(p_pfx), img.ptr(p_val), img.ptr(p_cr), img.ptr(p_tb), nd};
+    return VBF_OK;
+}
+
+constexpr uint64_t kGetMaxKeys = 0x7FFFFFFEull;
+
+// The argument checks of vbf_memtable_get_* that need no HIP call; *device = the handles' device, -1
+// when there is none.
+int memget_check(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, const vbf_memtable* gc,
+                 const vbf_memtable* active, uint32_t nro, const vbf_memtable* const* ro, const vbf_vlog* log,
+                 int* device) {
+    *device = -1;
+    if (n > kGetMaxKeys) return fail(VBF_EINVAL, "too many keys: %llu (limit 2^31 - 2)", (unsigned long long)n);
+    int rc = check_keys(keys, offsets, stride, n);
+    if (rc) return rc;
+    if (nro && !ro) return fail(VBF_EINVAL, "ro is NULL");
+    for (uint32_t i = 0; i < nro; ++i)
+        if (!ro[i]) return fail(VBF_EINVAL, "ro[%u] is NULL", i);
+    if (gc && !log) return fail(VBF_EINVAL, "a gc table needs the log: log is NULL");
+    auto same = [&](const char* what, int dev) {
+        if (*device < 0) *device = dev;
+        return *device == dev ? VBF_OK
+                              : fail(VBF_EINVAL, "%s lives on device %d, the other handles on %d", what, dev, *device);
+    };
+    if (gc && ((rc = same("gc", gc->device)) || (rc = same("log", log->device)))) return rc;
+    if (active && (rc = same("active", active->device))) return rc;
+    for (uint32_t i = 0; i < nro; ++i)
+        if ((rc = same("a read-only memtable", ro[i]->device))) return rc;
+    return VBF_OK;
+}
+
+bool memget_sampled() {  // VBF_MEMGET=0: the plain kernel (read per call; identical results)
+    const char* e = getenv("VBF_MEMGET");
+    return !(e && e[0] == '0' && !e[1]);
+}
+
+// Device pointers, on the handles' device: the layers' descriptors go up (one stream
+// synchronisation, their source is pageable), then the lookup is queued on `s`.
+int memget_lookup(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n, const vbf_memtable* gc,
+                  const vbf_memtable* active, uint32_t nro, const vbf_memtable* const* ro, const vbf_vlog* log,
+                  uint8_t* found, uint32_t* layer, uint32_t* val_offsets, uint64_t* created_ms, hipStream_t s) {
+    std::vector<vbf::MemDesc> tab(2 + (size_t)nro);
+    if (gc) tab[0] = gc->desc;
+    if (active) tab[1] = active->desc;
+    for (uint32_t i = 0; i < nro; ++i) tab[2 + i] = ro[i]->desc;
+    void* ws = nullptr;
+    int rc = get_workspace(s, tab.size() * sizeof(vbf::MemDesc), &ws, kWsMemGetDesc);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ws, tab.data(), tab.size() * sizeof(vbf::MemDesc), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    vbf::MemGetArgs a{};
+    a.keys = keys;
+    a.offsets = offsets;
+    a.stride = stride;
+    a.n = n;
+    a.layers = static_cast<const vbf::MemDesc*>(ws);
+    a.nro = nro;
+    if (gc) {
+        a.log = log->bytes;
+        a.log_len = log->len;
+        a.log_base = log->base;
+    }
+    a.found = found;
+    a.layer = layer;
+    a.val_off = val_offsets;
+    a.created = created_ms;
+    vbf::phase_begin(vbf::kPhaseMemGet, s);
+    HIP_TRY(vbf::mem_get(a, memget_sampled(), s));
+    vbf::phase_end(vbf::kPhaseMemGet, s);
+    return VBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbf_memtable_open_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                          const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones,
+                          void* stream, vbf_memtable** out) {
+    int rc = memtable_open_check(keys, offsets, stride, n, out);
+    if (rc) return rc;
+    FORK_GUARD();
+    try {
+        std::unique_ptr<vbf_memtable> t(new (std::nothrow) vbf_memtable());
+        if (!t) return table_no_memory();
+        HIP_TRY(hipGetDevice(&t->device));
+        if (n) {
+            hipStream_t s = (hipStream_t)stream;
+            uint64_t ends[2] = {0, n * stride};
+            if (offsets) {  // the key bytes' extent, read with the sort's count; the sort reports descending offsets
+                HIP_TRY(hipMemcpyAsync(&ends[0], offsets, 8, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(&ends[1], offsets + n, 8, hipMemcpyDeviceToHost, s));
+            }
+            rc = memtable_fill(*t, keys, offsets, stride, n, ends, val_offsets, created_ms, tombstones, s);
+            // the copies above and the gather read the caller's arrays and write the handle: complete on return
+            const hipError_t e = hipStreamSynchronize(s);
+            if (rc) return rc;
+            HIP_TRY(e);
+        }
+        *out = t.release();
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+int vbf_memtable_open_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                           const uint32_t* val_offsets, const int64_t* created_ms, const uint8_t* tombstones, int device,
+                           vbf_memtable** out) {
+    int rc = memtable_open_check(keys, offsets, stride, n, out);
+    if (rc || (rc = offsets_ascend(offsets, n))) return rc;
+    const uint64_t kb = !n ? 0 : (offsets ? offsets[n] - offsets[0] : n * stride);
+    if (!keys && kb) return fail(VBF_EINVAL, "keys is NULL");
+    try {
+        std::unique_ptr<vbf_memtable> t(new (std::nothrow) vbf_memtable());
+        if (!t) return table_no_memory();
+        t->device = device;
+        if (n) {
+            HOST_CALL(call, device);
+            KeyImage m;  // keys | offsets | val | created | tombstones
+            m.lay(offsets, stride, n);
+            const auto p_val = m.add<uint32_t>(n, val_offsets);
+            const auto p_cr = m.add<int64_t>(n, created_ms);
+            const auto p_tb = m.add<uint8_t>(n, tombstones);
+            if ((rc = m.alloc(call, kWsMemIO)) || (rc = m.upload(call, keys, offsets, n)) ||
+                (rc = call.up(m.ptr(p_val), val_offsets, n)) || (rc = call.up(m.ptr(p_cr), created_ms, n)) ||
+                (rc = call.up(m.ptr(p_tb), tombstones, n)))
+                return rc;
+            const uint64_t ends[2] = {0, kb};
+            if ((rc = memtable_fill(*t, m.ptr(m.keys), m.ptr(m.off), stride, n, ends, m.ptr(p_val), m.ptr(p_cr),
+                                    m.ptr(p_tb), call.s)))
+                return rc;
+            if ((rc = call.finish())) return rc;
+        }
+        *out = t.release();
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+void vbf_memtable_free(vbf_memtable* t) { delete t; }
+uint64_t vbf_memtable_entries(const vbf_memtable* t) { return t ? t->n : 0; }
+uint64_t vbf_memtable_key_bytes(const vbf_memtable* t) { return t ? t->key_bytes : 0; }
+int vbf_memtable_device(const vbf_memtable* t) { return t ? t->device : VBF_DEVICE_HOST; }
+
+int vbf_memtable_export_host(const vbf_memtable* t, uint8_t* keys, uint64_t keys_cap, uint64_t* key_off,
+                             uint32_t* val_offsets, int64_t* created_ms, uint8_t* tombstones, uint64_t entries_cap) {
+    if (!t) return fail(VBF_EINVAL, "memtable is NULL");
+    if (keys && keys_cap < t->key_bytes)
+        return fail(VBF_EINVAL, "keys_cap %llu < %llu key bytes", (unsigned long long)keys_cap,
+                    (unsigned long long)t->key_bytes);
+    if ((key_off || val_offsets || created_ms || tombstones) && entries_cap < t->n)
+        return fail(VBF_EINVAL, "entries_cap %llu < %llu entries", (unsigned long long)entries_cap,
+                    (unsigned long long)t->n);
+    if (!keys && !key_off && !val_offsets && !created_ms && !tombstones) return ok();  // sizes: the accessors
+    if (!t->n) {
+        if (key_off) key_off[0] = 0;
+        return ok();
+    }
+    HOST_CALL(call, t->device);
+    int rc;
+    if ((rc = call.down(keys, t->desc.keys, t->key_bytes)) || (rc = call.down(key_off, t->desc.off, t->n + 1)) ||
+        (rc = call.down(val_offsets, t->desc.val, t->n)) || (rc = call.down(created_ms, t->desc.created, t->n)) ||
+        (rc = call.down(tombstones, t->desc.tomb, t->n)))
+        return rc;
+    return call.finish();
+}
+
+// Flusher::flush of an open memtable: the encoder over the handle's arrays.
+int vbf_memtable_encode_host(const vbf_memtable* t, uint8_t* data, uint64_t data_cap, uint64_t* data_len, uint8_t* index,
+                             uint64_t index_cap, uint64_t* index_len) {
+    if (!data_len || !index_len) return fail(VBF_EINVAL, "data_len / index_len is NULL");
+    *data_len = *index_len = 0;
+    if (!t) return fail(VBF_EINVAL, "memtable is NULL");
+    if (!t->n) return fail(VBF_EINVAL, "Cannot flush an empty table (flusher.rs:40-44, table.rs:262-264)");
+    const uint64_t nd = t->n, kb = t->key_bytes;
+    if (nd >= (1ull << 32) / 17 || kb >= (1ull << 32))
+        return fail(VBF_EINVAL, "data.db reaches 2^32 bytes: index.db's u32 block offsets cannot address it");
+    HOST_CALL(call, t->device);
+    DevImage q;  // data.db | index.db; capacities that always suffice
+    const auto q_data = q.add<uint8_t>(kb + 17 * nd);
+    const auto q_idx = q.add<uint8_t>(kb + 8 * nd);
+    int rc = q.alloc(call, kWsMemOut);
+    if (rc) return rc;
+    uint64_t nb = 0;
+    if ((rc = sst_encode(t->desc.keys, t->desc.off, 0, nd, t->desc.val, t->desc.created, t->desc.tomb,
+                         data ? q.ptr(q_data) : nullptr, kb + 17 * nd, data_len, index ? q.ptr(q_idx) : nullptr,
+                         kb + 8 * nd, index_len, nullptr, 0, &nb, call.s)))
+        return rc;
+    if (data && data_cap < *data_len)
+        return fail(VBF_EINVAL, "data holds %llu < %llu bytes", (unsigned long long)data_cap,
+                    (unsigned long long)*data_len);
+    if (index && index_cap < *index_len)
+        return fail(VBF_EINVAL, "index holds %llu < %llu bytes", (unsigned long long)index_cap,
+                    (unsigned long long)*index_len);
+    if ((rc = call.down(data, q.ptr(q_data), *data_len)) || (rc = call.down(index, q.ptr(q_idx), *index_len))) return rc;
+    return call.finish();
+}
+
+int vbf_memtable_get_dev(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                         const vbf_memtable* gc, const vbf_memtable* active, uint32_t nro,
+                         const vbf_memtable* const* ro, const vbf_vlog* log, uint8_t* found, uint32_t* layer,
+                         uint32_t* val_offsets, uint64_t* created_ms, void* stream) {
+    int device = -1;
+    int rc = memget_check(keys, offsets, stride, n, gc, active, nro, ro, log, &device);
+    if (rc) return rc;
+    if (!n) return ok();
+    FORK_GUARD();
+    hipStream_t s = (hipStream_t)stream;
+    if (device < 0) {  // no memtable at all: nothing is found
+        if (found) HIP_TRY(hipMemsetAsync(found, 0, n, s));
+        if (layer) HIP_TRY(hipMemsetAsync(layer, 0xFF, n * 4, s));
+        if (val_offsets) HIP_TRY(hipMemsetAsync(val_offsets, 0, n * 4, s));
+        if (created_ms) HIP_TRY(hipMemsetAsync(created_ms, 0, n * 8, s));
+        return ok();
+    }
+    try {
+        DEVICE_SCOPE(device);
+        if ((rc = memget_lookup(keys, offsets, stride, n, gc, active, nro, ro, log, found, layer, val_offsets, created_ms, s)))
+            return rc;
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+    return ok();
+}
+
+int vbf_memtable_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                          const vbf_memtable* gc, const vbf_memtable* active, uint32_t nro,
+                          const vbf_memtable* const* ro, const vbf_vlog* log, uint8_t* found, uint32_t* layer,
+                          uint32_t* val_offsets, uint64_t* created_ms) {
+    int device = -1;
+    int rc = memget_check(keys, offsets, stride, n, gc, active, nro, ro, log, &device);
+    if (rc || (rc = offsets_ascend(offsets, n))) return rc;
+    if (!n) return ok();
+    if (device < 0) {
+        if (found) memset(found, 0, n);
+        if (layer) memset(layer, 0xFF, n * 4);
+        if (val_offsets) memset(val_offsets, 0, n * 4);
+        if (created_ms) memset(created_ms, 0, n * 8);
+        return ok();
+    }
+    try {
+        HOST_CALL(call, device);
+        KeyImage m;  // keys | offsets | found | layer | val_offsets | created
+        m.lay(offsets, stride, n);
+        const auto p_found = m.add<uint8_t>(n, found);
+        const auto p_layer = m.add<uint32_t>(n, layer);
+        const auto p_val = m.add<uint32_t>(n, val_offsets);
+        const auto p_cr = m.add<uint64_t>(n, created_ms);
+        if ((rc = m.alloc(call, kWsMemGetIO)) || (rc = m.upload(call, keys, offsets, n))) return rc;
+        if ((rc = memget_lookup(m.ptr(m.keys), m.ptr(m.off), stride, n, gc, active, nro, ro, log, m.ptr(p_found),
+                                m.ptr(p_layer), m.ptr(p_val), m.ptr(p_cr), call.s)))
+            return rc;
+        if ((rc = call.down(found, m.ptr(p_found), n)) || (rc = call.down(layer, m.ptr(p_layer), n)) ||
+            (rc = call.down(val_offsets, m.ptr(p_val), n)) || (rc = call.down(created_ms, m.ptr(p_cr), n)))
+            return rc;
+        return call.finish();
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+}
+
+// DataStore::get for a batch, bytes to values: the memtables, the tables for what they left open, the
+// merge and the value log, all on the log's device from one upload of the keys.
+int vbf_store_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t stride, uint64_t n,
+                       const vbf_memtable* gc, const vbf_memtable* active, uint32_t nro, const vbf_memtable* const* ro,
+                       uint32_t nsst, const vbf_table* const* tables, const vbf_filter* const* filters,
+                       const vbf_vlog* log, int check_keys_flag, uint8_t* found, uint32_t* layer, uint32_t* table_idx,
+                       uint32_t* val_offsets, uint64_t* created_ms, uint8_t* status, uint8_t* values,
+                       uint64_t values_cap, uint64_t* value_off, uint64_t* value_bytes) {
+    if (!value_bytes) return fail(VBF_EINVAL, "value_bytes is NULL");
+    *value_bytes = 0;
+    if (!log) return fail(VBF_EINVAL, "vlog is NULL");
+    int device = -1;
+    int rc = memget_check(keys, offsets, stride, n, gc, active, nro, ro, log, &device);
+    if (rc || (rc = offsets_ascend(offsets, n))) return rc;
+    if (nsst && !tables) return fail(VBF_EINVAL, "tables is NULL");
+    for (uint32_t i = 0; i < nsst; ++i)
+        if (!tables[i]) return fail(VBF_EINVAL, "tables[%u] is NULL", i);
+    if (!nsst) filters = nullptr;
+    if (filters)
+        for (uint32_t i = 0; i < nsst; ++i)
+            if (!filters[i]) return fail(VBF_EINVAL, "filters[%u] is NULL", i);
+    if (device >= 0 && device != log->device)
+        return fail(VBF_EINVAL, "the memtables live on device %d, the log on %d", device, log->device);
+    device = log->device;
+    for (uint32_t i = 0; i < nsst; ++i)
+        if (tables[i]->device != device)
+            return fail(VBF_EINVAL, "tables[%u] lives on device %d, the log on %d", i, tables[i]->device, device);
+    if (!n) {
+        if (value_off) value_off[0] = 0;
+        return ok();
+    }
+    try {
+        // Lock order as in vbf_table_get_host: the filters' locks and their drain, then the device.
+        MultiLock lk(filters, filters ? nsst : 0);
+        if ((rc = lk.drain())) return rc;
+        if (filters)
+            for (uint32_t i = 0; i < nsst; ++i)
+                if (filters[i]->bits->device != device)
+                    return fail(VBF_EINVAL, "filters[%u] lives on device %d, the log on %d", i,
+                                filters[i]->bits->device, device);
+        HOST_CALL(call, device);
+        hipStream_t s = call.s;
+        KeyImage m;  // keys | offsets | the merged answer | candidates | the tables' answer: 33 + nsst bytes per key
+        m.lay(offsets, stride, n);
+        const auto p_found = m.add<uint8_t>(n);
+        const auto p_layer = m.add<uint32_t>(n);
+        const auto p_val = m.add<uint32_t>(n);
+        const auto p_cr = m.add<uint64_t>(n);
+        const auto p_tidx = m.add<uint32_t>(n);
+        const auto p_cand = m.add<uint8_t>(n * nsst, nsst);
+        const auto t_found = m.add<uint8_t>(n, nsst);
+        const auto t_idx = m.add<uint32_t>(n, nsst);
+        const auto t_val = m.add<uint32_t>(n, nsst);
+        const auto t_cr = m.add<uint64_t>(n, nsst);
+        if ((rc = m.alloc(call, kWsStoreIO)) || (rc = m.upload(call, keys, offsets, n))) return rc;
+        const uint8_t* d_keys = m.ptr(m.keys);
+        const uint64_t* d_off = m.ptr(m.off);
+        if ((rc = memget_lookup(d_keys, d_off, stride, n, gc, active, nro, ro, log, m.ptr(p_found), m.ptr(p_layer),
+                                m.ptr(p_val), m.ptr(p_cr), s)))
+            return rc;
+        if (nsst) {
+            if (filters) {  // filter_sstables_by_key_range (range.rs:91-147) with the tables' own key ranges
+                std::vector<uint8_t> bounds;
+                std::vector<uint64_t> boff;
+                table_bounds(nsst, tables, &bounds, &boff);
+                if ((rc = multi_probe(d_keys, d_off, stride, n, 1, nsst, filters, bounds.data(), boff.data(),
+                                      m.ptr(p_cand), s)))
+                    return rc;
+            } else {
+                HIP_TRY(hipMemsetAsync(m.ptr(p_cand), 1, n * nsst, s));
+            }
+            HIP_TRY(vbf::store_cand(m.ptr(p_found), n, nsst, m.ptr(p_cand), s));
+            if ((rc = table_lookup(d_keys, d_off, stride, n, nsst, tables, m.ptr(p_cand), m.ptr(t_found), m.ptr(t_idx),
+                                   m.ptr(t_val), m.ptr(t_cr), s)))
+                return rc;
+        }
+        const vbf::StoreMergeArgs ma{n, m.ptr(p_found), m.ptr(p_layer), m.ptr(p_val), m.ptr(p_cr), m.ptr(t_found),
+                                     m.ptr(t_idx), m.ptr(t_val), m.ptr(t_cr), m.ptr(p_tidx)};
+        HIP_TRY(vbf::store_merge(ma, s));
+        vbf::VlogGetArgs a;
+        uint64_t total = 0;
+        if ((rc = vlog_get_sizes(log, m.ptr(p_val), m.ptr(p_found), n, check_keys_flag ? d_keys : nullptr, d_off, stride, s, &a, &total)))
+            return rc;
+        *value_bytes = total;
+        if ((rc = vlog_values_cap(values, values_cap, total))) return rc;
+        if ((rc = call.down(found, m.ptr(p_found), n)) || (rc = call.down(layer, m.ptr(p_layer), n)) ||
+            (rc = call.down(table_idx, m.ptr(p_tidx), n)) || (rc = call.down(val_offsets, m.ptr(p_val), n)) ||
+            (rc = call.down(created_ms, m.ptr(p_cr), n)) || (rc = call.down(status, a.status, n)) ||
+            (rc = call.down(value_off, a.voff, n + 1)))
+            return rc;
+        if (values && total) {
+            DevImage vals;
+            const auto p_values = vals.add<uint8_t>(total);
+            if ((rc = vals.alloc(call, kWsVlogOut))) return rc;
+            if ((rc = vlog_get_fill(a, vals.ptr(p_values), s)) || (rc = call.down(values, vals.ptr(p_values), total)))
                 return rc;
         }
         return call.finish();

@@ -34,7 +34,7 @@ enum Phase { kPhaseTileSort = 0, kPhaseTranspose = 1, kPhaseSegOr = 2, kPhaseAto
              kPhaseEncIndex = 16, kPhaseEncData = 17, kPhaseTableOpen = 18, kPhaseTableGet = 19,
              kPhaseScanRank = 20, kPhaseScanEmit = 21, kPhaseVlogSizes = 22, kPhaseVlogCopy = 23,
              kPhaseVlogEncode = 24, kPhaseMemSort = 25, kPhaseMemMerge = 26, kPhaseFilterInsert = 27,
-             kPhaseGcJudge = 28, kPhaseGcEmit = 29, kNumPhases = 30 };
+             kPhaseGcJudge = 28, kPhaseGcEmit = 29, kPhaseMemGet = 30, kNumPhases = 31 };
 void phase_begin(int phase, hipStream_t s);
 void phase_end(int phase, hipStream_t s);
 
@@ -365,6 +365,46 @@ struct GcArgs {
 hipError_t gc_overlay(const GcArgs& a, hipStream_t s);
 hipError_t gc_judge(const GcArgs& a, hipStream_t s);
 hipError_t gc_emit(const GcArgs& a, hipStream_t s);
+// Memtable lookups and the whole get (vbf_memget.hip).  A MemDesc is an open vbf_memtable: n distinct
+// keys ascending, key e = keys[off[e] .. off[e + 1]), pfx[e] its zero-padded big-endian 8-byte prefix.
+struct MemDesc {
+    const uint8_t* keys;
+    const uint64_t* off;
+    const uint64_t* pfx;
+    const uint32_t* val;
+    const int64_t* created;
+    const uint8_t* tomb;
+    uint64_t n;
+};
+struct MemGetArgs {
+    const uint8_t* keys;
+    const uint64_t* offsets;  // n + 1 absolute positions, or NULL for `stride`
+    uint64_t stride, n;
+    const MemDesc* layers;    // device, 2 + nro entries: the gc table, the active memtable (n = 0 when
+    uint32_t nro;             // absent), then the read-only memtables in the caller's order
+    const uint8_t* log;       // the log window, read only for hits in layer 0
+    uint64_t log_len, log_base;
+    uint8_t* found;           // outputs, each may be NULL
+    uint32_t* layer;
+    uint32_t* val_off;
+    uint64_t* created;
+};
+struct StoreMergeArgs {
+    uint64_t n;
+    uint8_t* found;           // the memtables' answers, merged in place
+    uint32_t* layer;
+    uint32_t* val_off;
+    uint64_t* created;
+    const uint8_t* t_found;   // the tables' answers, NULL without tables
+    const uint32_t* t_idx;
+    const uint32_t* t_val;
+    const uint64_t* t_created;
+    uint32_t* table_idx;      // out: the winning table, 0xFFFFFFFF when no table answered
+};
+hipError_t mem_prefixes(const uint8_t* keys, const uint64_t* off, uint64_t n, uint64_t* pfx, hipStream_t s);
+hipError_t mem_get(const MemGetArgs& a, bool sampled, hipStream_t s);
+hipError_t store_cand(const uint8_t* found, uint64_t n, uint32_t nsst, uint8_t* cand, hipStream_t s);
+hipError_t store_merge(const StoreMergeArgs& a, hipStream_t s);
 // Batched probe across SSTs (vbf_multi.hip).
 struct MultiSst {
     const uint32_t* words;

@@ -17,6 +17,14 @@ velarixdb_amd/csrc/vbf_memtable.hip).
   recover_puts(vlog, head_offset)      -> (keys, val_offsets, created_ms, tombstones): the recovered
                                        log's entries after the head entry, ready for sort_ids / flush
   BloomFilter.insert_many(keys)        the memtable's filter step, see filter.py
+  MemTable.open(keys, val_offsets, created_ms=None, tombstones=None)   -> MemTable: the puts sorted and
+                                       kept on the device (C ABI vbf_memtable_open_host), immutable
+  mt.export()                          -> MemEntries(keys, val_offsets, created_ms, tombstones), sorted
+  mt.flush()                           -> FlushResult: Flusher::flush of the open table
+  MemTable.get_many(keys, active=None, read_only=(), gc=None, vlog=None)
+      -> MemGet(found, layer, val_offsets, created_ms): steps 0-2 of DataStore::get (store.rs:442-472)
+      for a batch -- the gc table, the active memtable, the read-only ones -- on the device
+      (vbf_memtable_get_host, velarixdb_amd/csrc/vbf_memget.hip); store.get_many goes on to the values
 
 `filter` (a device-resident BloomFilter on `device`) takes MemTable::insert's filter step over
 every put in order.  Cutting a put stream into memtables by capacity (is_full, mem.rs:277-279),
@@ -29,9 +37,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import VbfError, call
+from ._lib import VbfError, call, lib
 from .filter import _raise
-from .keys import HostBatch, pack
+from .keys import HostBatch, pack, pack_offsets
 from .sst import DATA_FILE_NAME, INDEX_FILE_NAME
 from .vlog import ValueLog
 
@@ -130,3 +138,122 @@ def flush_to_dir(sst_dir, keys, val_offsets, created_ms=None, tombstones=None, f
     with open(os.path.join(sst_dir, INDEX_FILE_NAME + ".db"), "wb") as f:
         f.write(res.index.tobytes())
     return res
+
+
+LAYER_GC, LAYER_ACTIVE, LAYER_READ_ONLY, LAYER_NONE = 0, 1, 2, 0xFFFFFFFF
+LAYER_TABLE = 0x80000000  # store.get_many: layer = LAYER_TABLE | index into `tables`
+
+
+@dataclass
+class MemEntries:
+    keys: HostBatch          # the distinct keys ascending (offsets from 0)
+    val_offsets: np.ndarray  # uint32
+    created_ms: np.ndarray   # int64
+    tombstones: np.ndarray   # uint8
+
+
+@dataclass
+class MemGet:
+    found: np.ndarray        # uint8: 0 in no memtable, 1 live, 2 tombstone
+    layer: np.ndarray        # uint32: LAYER_GC, LAYER_ACTIVE, LAYER_READ_ONLY + r, LAYER_NONE
+    val_offsets: np.ndarray  # uint32
+    created_ms: np.ndarray   # uint64: the winner's created_at bits
+
+
+def _handles(tabs):
+    tabs = list(tabs)
+    return tabs, (ctypes.c_void_p * max(len(tabs), 1))(*[t._h.value for t in tabs])
+
+
+class MemTable:
+    """An immutable memtable resident on `device`: the puts it was opened from, sorted, last put wins."""
+
+    def __init__(self, _handle):
+        self._h = _handle
+
+    @classmethod
+    def open(cls, keys, val_offsets, created_ms=None, tombstones=None, device=0):
+        """MemTable::insert (mem.rs:207-221) for the puts `keys` in arrival order."""
+        b = _batch(keys)
+        n = b.n
+        arr = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
+        vo, cr, tb = arr(val_offsets, np.uint32), arr(created_ms, np.int64), arr(tombstones, np.uint8)
+        if any(x is not None and x.size != n for x in (vo, cr, tb)):
+            raise ValueError("one val_offset / created_ms / tombstone per key")
+        vp = lambda x: x.ctypes.data if x is not None and x.size else None
+        d, o = b.ptrs()
+        h = ctypes.c_void_p()
+        try:
+            call("vbf_memtable_open_host", d, o, b.stride, n, vp(vo), vp(cr), vp(tb), int(device), ctypes.byref(h))
+        except VbfError as e:
+            _raise("memtable_open", e)
+        return cls(h)
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            lib.vbf_memtable_free(h)
+        self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def entries(self):
+        return lib.vbf_memtable_entries(self._h)
+
+    @property
+    def key_bytes(self):
+        return lib.vbf_memtable_key_bytes(self._h)
+
+    @property
+    def device(self):
+        return lib.vbf_memtable_device(self._h)
+
+    def export(self):
+        """The sorted entries, in the layout of gc.collect_device's overlay."""
+        n, kb = self.entries, self.key_bytes
+        keys, off = np.zeros(kb + 1, np.uint8), np.zeros(n + 1, np.uint64)
+        vo, cr, tb = np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.int64), np.zeros(n + 1, np.uint8)
+        try:
+            call("vbf_memtable_export_host", self._h, keys.ctypes.data, kb, off.ctypes.data, vo.ctypes.data, cr.ctypes.data,
+                 tb.ctypes.data, n)
+        except VbfError as e:
+            _raise("memtable_export", e)
+        return MemEntries(pack_offsets(keys[:kb], off), vo[:n], cr[:n], tb[:n])
+
+    def flush(self):
+        """Flusher::flush of this table -> FlushResult; `ids` is None (the handle holds no put indices).
+        An empty table raises AssertionError ("Cannot flush an empty table", flusher.rs:40-44)."""
+        n, kb = self.entries, self.key_bytes
+        data, index = np.zeros(kb + 17 * n + 1, np.uint8), np.zeros(kb + 8 * n + 1, np.uint8)
+        dl, il = ctypes.c_uint64(), ctypes.c_uint64()
+        try:
+            call("vbf_memtable_encode_host", self._h, data.ctypes.data, data.size, ctypes.byref(dl), index.ctypes.data,
+                 index.size, ctypes.byref(il))
+        except VbfError as e:
+            _raise("memtable_encode", e)
+        ent = self.export()
+        return FlushResult(data[:dl.value].copy(), index[:il.value].copy(), None, _key(ent.keys, 0), _key(ent.keys, n - 1))
+
+    @staticmethod
+    def get_many(keys, active=None, read_only=(), gc=None, vlog=None):
+        """Steps 0-2 of DataStore::get for every key: `gc` (needs `vlog`: a gc hit stands only with a
+        live value in the log), then `active`, then the newest of `read_only` -> MemGet."""
+        b = _batch(keys)
+        ro, rh = _handles(read_only)
+        res = MemGet(np.zeros(b.n, np.uint8), np.zeros(b.n, np.uint32), np.zeros(b.n, np.uint32), np.zeros(b.n, np.uint64))
+        d, o = b.ptrs()
+        vp = lambda x: x.ctypes.data if x.size else None
+        h = lambda t: t._h if t is not None else None
+        try:
+            call("vbf_memtable_get_host", d, o, b.stride, b.n, h(gc), h(active), len(ro), rh, h(vlog), vp(res.found),
+                 vp(res.layer), vp(res.val_offsets), vp(res.created_ms))
+        except VbfError as e:
+            _raise("memtable_get", e)
+        return res
