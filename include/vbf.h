@@ -1118,6 +1118,57 @@ int vbf_store_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t st
                        uint64_t* created_ms, uint8_t* status, uint8_t* values, uint64_t values_cap,
                        uint64_t* value_off, uint64_t* value_bytes);
 
+/* DataStore::seek (src/range/range_iterator.rs:47-60, a stub in the reference) for a batch of ranges
+ * over the whole store, from bounds to values in one device pass.  The scan has no semantics of its
+ * own: for range r let U_r be the distinct keys k with lo_r <= k <= hi_r (Rust's `Ord for [u8]`;
+ * lo_r <= k < hi_r with VBF_SCAN_END_EXCLUSIVE) held by any of gc, active, ro[0..nro) and
+ * tables[0..nsst).  The scan of r lists, in ascending key order, every k of U_r for which
+ * vbf_store_get_host over the same handles in the same order, with filters == NULL and the same
+ * check_keys, reports found != 0, with exactly that call's layer, table_idx, val_offsets, created_ms,
+ * status and value.  A key with found == 2 is listed with tombstones[i] = 1 only under
+ * VBF_SCAN_KEEP_TOMBSTONES and omitted without it; either way the deciding tombstone hides everything
+ * below it.  Every rule of the get carries over because the definition is the get: the gc layer's
+ * fall-through on a tombstone entry or a NONE / TOMBSTONE log status, a BAD gc offset keeping its hit,
+ * the active memtable with no fall-through, signed times and "time <= 0 never wins" for the read-only
+ * memtables, created_at == 0 never winning in a table.  A key that only non-winning copies hold
+ * belongs to U_r and is not listed.
+ * bounds / bounds_off and the flags are vbf_table_scan_host's, and so are its rules for the ends:
+ * lo_r > hi_r is an empty range, not an error, and so is lo_r == hi_r with END_EXCLUSIVE; a
+ * zero-length lo_r starts at the first key, and a zero-length key is an ordinary key.
+ * Outputs (host arrays): range_off, keys, key_off, table_idx, val_offsets, created_ms and tombstones
+ * as vbf_table_scan_host writes them (table_idx[i] = 0xFFFFFFFF when a memtable answered); layer[i] as
+ * vbf_store_get_host writes it; status, values and value_off as vbf_vlog_get_host over the listed
+ * entries (the fetch runs for tombstones[i] == 0, the rest are SKIPPED; value_off has n_out + 1
+ * entries, so entries_cap + 1 slots, as key_off).  *n_out, *key_bytes and *value_bytes are always
+ * written.  Every output array may be NULL; all of them NULL is the size query.  A capacity that is
+ * too small -- entries_cap < *n_out with any per-entry array given, keys_cap < *key_bytes with keys
+ * given, values_cap < *value_bytes with values given -- is VBF_EINVAL with the three sizes written
+ * and no output array touched.
+ * nranges == 0 is VBF_OK with zero sizes and no device work, and writes range_off[0] = key_off[0] =
+ * value_off[0] = 0.  `log` is required; gc, active, nro = 0 and nsst = 0 may all be absent, and with
+ * no layer at all every range is empty, with no device work.  Everything lives on the log's device
+ * (VBF_EINVAL otherwise).  Every argument check (NULL pointers, unknown flag bits, a handle on another
+ * device, a descending bounds_off, gc without log) runs on the host before any HIP call.  The
+ * candidate entries -- the sum, over ranges and layers, of the layer's entries inside the range --
+ * are limited to 2^31 - 1, VBF_EINVAL "too many entries" beyond; so are the (range, layer) pairs.
+ * Work is O(candidates x layers x log(entries per layer)) key comparisons: every candidate searches
+ * its key in every other layer (csrc/vbf_store_scan.hip).  That suits short and medium ranges; it is
+ * not a merge-path scan.
+ * Synchronous; the device's lock as vbf_store_get_host takes it.  Workspace (cached per stream like
+ * every other): the bounds, 64 bytes per layer, 24 per (range, layer) pair, 61 per candidate, 30 per
+ * listed entry plus the listed keys, the scans' scratch, and vbf_vlog_get_host's for the listed
+ * entries.  Stream synchronisations: the layers' descriptors, the candidate total, the entry and key
+ * sizes, the value bytes' total, one at the end. */
+int vbf_store_scan_host(const uint8_t* bounds, const uint64_t* bounds_off, uint64_t nranges,
+                        const vbf_memtable* gc, const vbf_memtable* active, uint32_t nro,
+                        const vbf_memtable* const* ro, uint32_t nsst, const vbf_table* const* tables,
+                        const vbf_vlog* log, uint32_t flags, int check_keys,
+                        uint64_t* range_off, uint8_t* keys, uint64_t keys_cap, uint64_t* key_off,
+                        uint8_t* tombstones, uint32_t* layer, uint32_t* table_idx, uint32_t* val_offsets,
+                        uint64_t* created_ms, uint8_t* status, uint64_t entries_cap,
+                        uint8_t* values, uint64_t values_cap, uint64_t* value_off,
+                        uint64_t* n_out, uint64_t* key_bytes, uint64_t* value_bytes);
+
 #ifdef __cplusplus
 }
 #endif

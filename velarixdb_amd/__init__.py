@@ -13,6 +13,7 @@ from .table import GetResult, ScanResult, Table, get_many, get_values, scan_many
 from .vlog import ValueLog, Values, Walk  # noqa: F401
 from .gc import GcResult, collect_device  # noqa: F401
 from .memtable import MemTable  # noqa: F401
+from .store import StoreScan, scan_many as store_scan_many  # noqa: F401
 from . import compaction, gc, key_range, memtable, sst, store, table, vlog  # noqa: F401
 
 __version__ = "0.1.0"

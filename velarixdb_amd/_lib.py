@@ -180,6 +180,9 @@ SIGNATURES = {
     "vbf_memtable_get_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vbf_store_get_host": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _int, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64)]),
+    "vbf_store_scan_host": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _int, _vp, _vp, _u64, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(_u64),
+                                    ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
 }
 
 

@@ -187,6 +187,11 @@ enum WsSlot {
     kWsMemGetDesc = 36,
     kWsMemGetIO = 37,
     kWsStoreIO = 38,
+    kWsStoreScanDesc = 39,
+    kWsStoreScanIn = 40,
+    kWsStoreScanPairs = 41,
+    kWsStoreScan = 42,
+    kWsStoreScanOut = 43,
 };
 struct Workspace {
     int device;
@@ -5585,6 +5590,272 @@ int vbf_store_get_host(const uint8_t* keys, const uint64_t* offsets, uint64_t st
             const auto p_values = vals.add<uint8_t>(total);
             if ((rc = vals.alloc(call, kWsVlogOut))) return rc;
             if ((rc = vlog_get_fill(a, vals.ptr(p_values), s)) || (rc = call.down(values, vals.ptr(p_values), total)))
+                return rc;
+        }
+        return call.finish();
+    } catch (const std::bad_alloc&) {
+        return table_no_memory();
+    }
+}
+
+}  // extern "C"
+
+// ---- range scans over the whole store (DataStore::seek with vbf_store_get_host as the lookup) ----
+
+namespace {
+
+struct StoreScanOut {
+    uint64_t* range_off;
+    uint8_t* keys;
+    uint64_t* key_off;
+    uint8_t* tombstones;
+    uint32_t* layer;
+    uint32_t* table_idx;
+    uint32_t* val_offsets;
+    uint64_t* created_ms;
+    uint8_t* status;
+    uint8_t* values;
+    uint64_t* value_off;
+    bool per_entry() const {
+        return key_off || tombstones || layer || table_idx || val_offsets || created_ms || status || value_off;
+    }
+    bool any() const { return range_off || keys || values || per_entry(); }
+    void empty(uint64_t nranges) const {  // every range is empty
+        if (range_off) memset(range_off, 0, (nranges + 1) * 8);
+        if (key_off) key_off[0] = 0;
+        if (value_off) value_off[0] = 0;
+    }
+};
+
+// The bounds pass, the rank pass and the two scans on the log's device (bounds / bounds_off there).
+// Three stream synchronisations: the descriptors' upload, the candidate total, then *n_out and
+// *key_bytes.  `a` comes back ready for the emit passes; total == 0 ends after the second.
+// Workspace: 64 bytes per layer for the descriptors at most, 24 per (range, layer) pair, 61 per
+// candidate (listed flag and key length as u64 for scan_u64, their two scans, the key's address, the
+// get's answer: time, layer, table, offset, found), plus the scans' scratch.
+int store_scan_sizes(const uint8_t* bounds, const uint64_t* bounds_off, uint64_t nranges, const vbf_memtable* gc,
+                     const vbf_memtable* active, uint32_t nro, const vbf_memtable* const* ro, uint32_t nsst,
+                     const vbf_table* const* tables, const vbf_vlog* log, uint32_t flags, hipStream_t s,
+                     vbf::StoreScanArgs* a, uint64_t* n_out, uint64_t* key_bytes) {
+    *a = vbf::StoreScanArgs{};
+    a->bounds = bounds;
+    a->bounds_off = bounds_off;
+    a->nranges = nranges;
+    a->nmem = 2 + nro;
+    a->nsst = nsst;
+    a->flags = flags;
+    a->log = log->bytes;
+    a->log_len = log->len;
+    a->log_base = log->base;
+    std::vector<vbf::MemDesc> mem(a->nmem);
+    if (gc) mem[0] = gc->desc;
+    if (active) mem[1] = active->desc;
+    for (uint32_t i = 0; i < nro; ++i) mem[2 + i] = ro[i]->desc;
+    std::vector<vbf::TableDesc> tab(nsst);
+    for (uint32_t i = 0; i < nsst; ++i) tab[i] = tables[i]->desc;
+    const uint64_t mb = mem.size() * sizeof(vbf::MemDesc), tb = tab.size() * sizeof(vbf::TableDesc);
+    void* ws = nullptr;
+    int rc = get_workspace(s, align256(mb) + tb, &ws, kWsStoreScanDesc);
+    if (rc) return rc;
+    char* db = static_cast<char*>(ws);
+    HIP_TRY(hipMemcpyAsync(db, mem.data(), mb, hipMemcpyHostToDevice, s));
+    if (tb) HIP_TRY(hipMemcpyAsync(db + align256(mb), tab.data(), tb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // pageable sources
+    a->mem = reinterpret_cast<const vbf::MemDesc*>(db);
+    a->tab = reinterpret_cast<const vbf::TableDesc*>(db + align256(mb));
+    const uint64_t P = nranges * (a->nmem + nsst);
+    size_t tmpb = 0;
+    HIP_TRY(vbf::scan_u64(nullptr, &tmpb, nullptr, nullptr, P + 1, s));
+    const uint64_t o_cnt = align256(P * 8), o_cbase = o_cnt + align256((P + 1) * 8);
+    const uint64_t o_err = o_cbase + align256((P + 1) * 8), o_tmp = o_err + 256;
+    if ((rc = get_workspace(s, o_tmp + tmpb, &ws, kWsStoreScanPairs))) return rc;
+    char* pb = static_cast<char*>(ws);
+    a->first = reinterpret_cast<uint64_t*>(pb);
+    a->cnt = reinterpret_cast<uint64_t*>(pb + o_cnt);
+    uint64_t* cbase = reinterpret_cast<uint64_t*>(pb + o_cbase);
+    a->cbase = cbase;
+    a->err = reinterpret_cast<uint32_t*>(pb + o_err);
+    HIP_TRY(hipMemsetAsync(a->cnt + P, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(a->err, 0, 4, s));
+    vbf::phase_begin(vbf::kPhaseScanRank, s);
+    HIP_TRY(vbf::store_scan_bounds(*a, s));
+    HIP_TRY(vbf::scan_u64(pb + o_tmp, &tmpb, a->cnt, cbase, P + 1, s));
+    vbf::phase_end(vbf::kPhaseScanRank, s);
+    uint64_t total = 0;
+    uint32_t ev = 0;
+    HIP_TRY(hipMemcpyAsync(&total, cbase + P, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&ev, a->err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (ev & vbf::kScanErrBounds) return fail(VBF_EINVAL, "bounds_off is not nondecreasing");
+    if (total > 0x7FFFFFFFull)
+        return fail(VBF_EINVAL, "too many entries: %llu candidates in the ranges (limit 2^31 - 1)",
+                    (unsigned long long)total);
+    a->total = total;
+    *n_out = *key_bytes = 0;
+    if (!total) return VBF_OK;
+    size_t tmpc = 0;
+    HIP_TRY(vbf::scan_u64(nullptr, &tmpc, nullptr, nullptr, total + 1, s));
+    const uint64_t q_len = (total + 1) * 8, q_opos = align256(q_len + (total + 1) * 8);
+    const uint64_t q_kofs = q_opos + align256((total + 1) * 8), q_src = q_kofs + align256((total + 1) * 8);
+    const uint64_t q_cr = q_src + align256(total * 8), q_layer = q_cr + align256(total * 8);
+    const uint64_t q_tidx = q_layer + align256(total * 4), q_val = q_tidx + align256(total * 4);
+    const uint64_t q_found = q_val + align256(total * 4), q_tmp = q_found + align256(total);
+    if ((rc = get_workspace(s, q_tmp + tmpc, &ws, kWsStoreScan))) return rc;
+    char* cb = static_cast<char*>(ws);
+    a->m_keep = reinterpret_cast<uint64_t*>(cb);
+    a->m_len = reinterpret_cast<uint64_t*>(cb + q_len);
+    uint64_t* opos = reinterpret_cast<uint64_t*>(cb + q_opos);
+    uint64_t* kofs = reinterpret_cast<uint64_t*>(cb + q_kofs);
+    a->opos = opos;
+    a->kofs = kofs;
+    a->m_src = reinterpret_cast<const uint8_t**>(cb + q_src);
+    a->m_created = reinterpret_cast<uint64_t*>(cb + q_cr);
+    a->m_layer = reinterpret_cast<uint32_t*>(cb + q_layer);
+    a->m_tidx = reinterpret_cast<uint32_t*>(cb + q_tidx);
+    a->m_val = reinterpret_cast<uint32_t*>(cb + q_val);
+    a->m_found = reinterpret_cast<uint8_t*>(cb + q_found);
+    HIP_TRY(hipMemsetAsync(a->m_keep, 0, (total + 1) * 16, s));  // m_keep | m_len
+    vbf::phase_begin(vbf::kPhaseScanRank, s);
+    HIP_TRY(vbf::store_scan_rank(*a, s));
+    HIP_TRY(vbf::scan_u64(cb + q_tmp, &tmpc, a->m_keep, opos, total + 1, s));
+    HIP_TRY(vbf::scan_u64(cb + q_tmp, &tmpc, a->m_len, kofs, total + 1, s));
+    vbf::phase_end(vbf::kPhaseScanRank, s);
+    HIP_TRY(hipMemcpyAsync(n_out, opos + total, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(key_bytes, kofs + total, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&ev, a->err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (ev & vbf::kScanErrRank) {
+        *n_out = *key_bytes = 0;
+        return fail(VBF_EINVAL, "a merged rank fell outside its range: a layer's buffers changed since open");
+    }
+    return VBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbf_store_scan_host(const uint8_t* bounds, const uint64_t* bounds_off, uint64_t nranges, const vbf_memtable* gc,
+                        const vbf_memtable* active, uint32_t nro, const vbf_memtable* const* ro, uint32_t nsst,
+                        const vbf_table* const* tables, const vbf_vlog* log, uint32_t flags, int check_keys_flag,
+                        uint64_t* range_off, uint8_t* keys, uint64_t keys_cap, uint64_t* key_off, uint8_t* tombstones,
+                        uint32_t* layer, uint32_t* table_idx, uint32_t* val_offsets, uint64_t* created_ms,
+                        uint8_t* status, uint64_t entries_cap, uint8_t* values, uint64_t values_cap,
+                        uint64_t* value_off, uint64_t* n_out, uint64_t* key_bytes, uint64_t* value_bytes) {
+    if (!n_out || !key_bytes || !value_bytes) return fail(VBF_EINVAL, "n_out / key_bytes / value_bytes is NULL");
+    *n_out = *key_bytes = *value_bytes = 0;
+    int device = -1;
+    int rc = memget_check(nullptr, nullptr, 0, 0, gc, active, nro, ro, log, &device);  // the handles: no key batch here
+    if (rc) return rc;
+    if (!log) return fail(VBF_EINVAL, "vlog is NULL");
+    if (flags & ~(uint32_t)(VBF_SCAN_KEEP_TOMBSTONES | VBF_SCAN_END_EXCLUSIVE))
+        return fail(VBF_EINVAL, "unknown flags 0x%x", flags);
+    if (nsst && !tables) return fail(VBF_EINVAL, "tables is NULL");
+    for (uint32_t i = 0; i < nsst; ++i)
+        if (!tables[i]) return fail(VBF_EINVAL, "tables[%u] is NULL", i);
+    if (nranges && !bounds_off) return fail(VBF_EINVAL, "bounds_off is NULL");
+    if (nranges && !bounds) return fail(VBF_EINVAL, "bounds is NULL");
+    // the (range, layer) pairs are scanned like the candidates: below 2^31 items
+    const uint64_t nl = 2 + (uint64_t)nro + nsst;
+    if (nranges > 0x7FFFFFFEull / nl)
+        return fail(VBF_EINVAL, "too many entries: %llu ranges x %llu layers", (unsigned long long)nranges,
+                    (unsigned long long)nl);
+    for (uint64_t i = 0; i < 2 * nranges; ++i)
+        if (bounds_off[i] > bounds_off[i + 1])
+            return fail(VBF_EINVAL, "bounds_off decreases at entry %llu", (unsigned long long)(i + 1));
+    const StoreScanOut o{range_off, keys, key_off, tombstones, layer, table_idx, val_offsets, created_ms, status,
+                         values, value_off};
+    const bool layers = gc || active || nro || nsst;
+    if (layers) {  // everything on the log's device
+        if (device >= 0 && device != log->device)
+            return fail(VBF_EINVAL, "the memtables live on device %d, the log on %d", device, log->device);
+        for (uint32_t i = 0; i < nsst; ++i)
+            if (tables[i]->device != log->device)
+                return fail(VBF_EINVAL, "tables[%u] lives on device %d, the log on %d", i, tables[i]->device,
+                            log->device);
+    }
+    if (!nranges || !layers) {  // nothing to scan: every range is empty, no device work
+        o.empty(nranges);
+        return ok();
+    }
+    try {
+        HOST_CALL(call, log->device);
+        hipStream_t s = call.s;
+        // bounds and their offsets, rebased to positions in the device copy
+        const uint64_t b0 = bounds_off[0], bbytes = bounds_off[2 * nranges] - b0;
+        DevImage in;
+        const auto p_bounds = in.add<uint8_t>(bbytes + 1);
+        const auto p_boff = in.add<uint64_t>(2 * nranges + 1);
+        if ((rc = in.alloc(call, kWsStoreScanIn))) return rc;
+        if ((rc = call.up(in.ptr(p_bounds), bbytes ? bounds + b0 : nullptr, bbytes)) ||
+            (rc = call.up_rebased(in.ptr(p_boff), bounds_off, 2 * nranges + 1)))
+            return rc;  // pageable sources: store_scan_sizes synchronises before it launches
+        vbf::StoreScanArgs a;
+        if ((rc = store_scan_sizes(in.ptr(p_bounds), in.ptr(p_boff), nranges, gc, active, nro, ro, nsst, tables, log,
+                                   flags, s, &a, n_out, key_bytes)))
+            return rc;
+        const uint64_t n = *n_out, kb = *key_bytes;
+        if (!n) {  // nothing listed: store_scan_sizes returned synchronised
+            call.settled();
+            o.empty(nranges);
+            return ok();
+        }
+        if (n > kGetMaxKeys)  // the value lengths' scan runs over n + 1 items
+            return fail(VBF_EINVAL, "too many entries: %llu listed (limit 2^31 - 2)", (unsigned long long)n);
+        // The listed entries on the device: the emit passes fill them, the value fetch reads them, the
+        // capacity rule is applied once all three sizes are known, and only then anything goes down.
+        DevImage out;
+        const auto p_roff = out.add<uint64_t>(nranges + 1);
+        const auto p_koff = out.add<uint64_t>(n + 1);
+        const auto p_cr = out.add<uint64_t>(n);
+        const auto p_layer = out.add<uint32_t>(n);
+        const auto p_idx = out.add<uint32_t>(n);
+        const auto p_val = out.add<uint32_t>(n);
+        const auto p_tomb = out.add<uint8_t>(n);
+        const auto p_found = out.add<uint8_t>(n);
+        const auto p_keys = out.add<uint8_t>(kb + 1, keys || check_keys_flag);
+        if ((rc = out.alloc(call, kWsStoreScanOut))) return rc;
+        a.range_off = out.ptr(p_roff);
+        a.keys = out.ptr(p_keys);
+        a.key_off = out.ptr(p_koff);
+        a.tomb = out.ptr(p_tomb);
+        a.layer = out.ptr(p_layer);
+        a.table_idx = out.ptr(p_idx);
+        a.val_off = out.ptr(p_val);
+        a.created = out.ptr(p_cr);
+        a.found = out.ptr(p_found);
+        vbf::phase_begin(vbf::kPhaseScanEmit, s);
+        HIP_TRY(vbf::store_scan_emit(a, s));
+        HIP_TRY(vbf::store_scan_keys(a, s));
+        vbf::phase_end(vbf::kPhaseScanEmit, s);
+        vbf::VlogGetArgs va;
+        uint64_t total = 0;
+        if ((rc = vlog_get_sizes(log, a.val_off, a.found, n, check_keys_flag ? a.keys : nullptr, a.key_off, 0, s, &va,
+                                 &total)))
+            return rc;
+        *value_bytes = total;
+        if (o.per_entry() && entries_cap < n)
+            return fail(VBF_EINVAL, "entries_cap %llu < %llu listed entries", (unsigned long long)entries_cap,
+                        (unsigned long long)n);
+        if (keys && keys_cap < kb)
+            return fail(VBF_EINVAL, "keys_cap %llu < %llu key bytes", (unsigned long long)keys_cap,
+                        (unsigned long long)kb);
+        if ((rc = vlog_values_cap(values, values_cap, total))) return rc;
+        if (!o.any()) {  // the size query: vlog_get_sizes returned synchronised
+            call.settled();
+            return ok();
+        }
+        if ((rc = call.down(range_off, a.range_off, nranges + 1)) || (rc = call.down(key_off, a.key_off, n + 1)) ||
+            (rc = call.down(keys, a.keys, kb)) || (rc = call.down(tombstones, a.tomb, n)) ||
+            (rc = call.down(layer, a.layer, n)) || (rc = call.down(table_idx, a.table_idx, n)) ||
+            (rc = call.down(val_offsets, a.val_off, n)) || (rc = call.down(created_ms, a.created, n)) ||
+            (rc = call.down(status, va.status, n)) || (rc = call.down(value_off, va.voff, n + 1)))
+            return rc;
+        if (values && total) {
+            DevImage vals;
+            const auto p_values = vals.add<uint8_t>(total);
+            if ((rc = vals.alloc(call, kWsVlogOut))) return rc;
+            if ((rc = vlog_get_fill(va, vals.ptr(p_values), s)) || (rc = call.down(values, vals.ptr(p_values), total)))
                 return rc;
         }
         return call.finish();

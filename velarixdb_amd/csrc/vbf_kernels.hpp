@@ -405,6 +405,48 @@ hipError_t mem_prefixes(const uint8_t* keys, const uint64_t* off, uint64_t n, ui
 hipError_t mem_get(const MemGetArgs& a, bool sampled, hipStream_t s);
 hipError_t store_cand(const uint8_t* found, uint64_t n, uint32_t nsst, uint8_t* cand, hipStream_t s);
 hipError_t store_merge(const StoreMergeArgs& a, hipStream_t s);
+// Range scans over the whole store (vbf_store_scan.hip).  nl = nmem + nsst layers in DataStore::get's
+// order: the gc table, the active memtable (n = 0 when absent), the read-only memtables, the tables.
+// P = nranges * nl (range, layer) pairs in range-major order; `total` candidate entries, one merged
+// slot each.  Flags and error bits are the table scan's (kScan*).
+struct StoreScanArgs {
+    const uint8_t* bounds;      // device; lo_r / hi_r as in TableScanArgs
+    const uint64_t* bounds_off; // device, 2 * nranges + 1 absolute positions
+    uint64_t nranges;
+    uint32_t nmem, nsst, flags; // nmem = 2 + nro
+    const MemDesc* mem;         // device, nmem entries
+    const TableDesc* tab;       // device, nsst entries, in the caller's table order
+    const uint8_t* log;         // the log window, read only for hits in layer 0
+    uint64_t log_len, log_base;
+    uint64_t* first;            // [P] rank of the pair's first candidate in its layer (bounds pass)
+    uint64_t* cnt;              // [P + 1] candidates of the pair (bounds pass); [P] = 0
+    const uint64_t* cbase;      // [P + 1] exclusive scan of cnt; [P] = total
+    uint64_t total;
+    uint64_t* m_keep;           // [total + 1] 1 when the slot's key is listed, its key length then
+    uint64_t* m_len;            //             (rank pass; [total] = 0)
+    const uint8_t** m_src;      // [total] listed slots: the key's bytes in its first layer,
+    uint64_t* m_created;        //         and the get's answer for it (rank pass)
+    uint32_t* m_layer;
+    uint32_t* m_tidx;
+    uint32_t* m_val;
+    uint8_t* m_found;
+    const uint64_t* opos;       // [total + 1] exclusive scans of m_keep / m_len
+    const uint64_t* kofs;
+    uint32_t* err;              // [0] kScanErr bits
+    uint64_t* range_off;        // outputs, each may be NULL (emit / keys passes)
+    uint8_t* keys;
+    uint64_t* key_off;
+    uint8_t* tomb;
+    uint32_t* layer;
+    uint32_t* table_idx;
+    uint32_t* val_off;
+    uint64_t* created;
+    uint8_t* found;             // 1 live / 2 tombstone per listed entry: the value fetch's `found`
+};
+hipError_t store_scan_bounds(const StoreScanArgs& a, hipStream_t s);
+hipError_t store_scan_rank(const StoreScanArgs& a, hipStream_t s);
+hipError_t store_scan_emit(const StoreScanArgs& a, hipStream_t s);
+hipError_t store_scan_keys(const StoreScanArgs& a, hipStream_t s);
 // Batched probe across SSTs (vbf_multi.hip).
 struct MultiSst {
     const uint32_t* words;

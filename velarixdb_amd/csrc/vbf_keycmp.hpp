@@ -6,17 +6,11 @@
 #include <stdint.h>
 
 #include "vbf_kernels.hpp"
+#include "vbf_keyprefix.hpp"
 
 namespace vbf {
 
-// 8 bytes at a time as big-endian words (global memory takes unaligned 8-byte loads), then the
-// tail byte by byte.
-__device__ __forceinline__ uint64_t ld_be64(const uint8_t* p) {
-    uint64_t w;
-    __builtin_memcpy(&w, p, 8);
-    return __builtin_bswap64(w);
-}
-
+// 8 bytes at a time as big-endian words, then the tail byte by byte.
 __device__ __forceinline__ int cmp_keys(const uint8_t* ka, uint64_t la, const uint8_t* kb, uint64_t lb) {
     const uint64_t n = la < lb ? la : lb;
     uint64_t i = 0;
@@ -34,14 +28,6 @@ __device__ __forceinline__ int cmp_keys(const uint8_t* ka, uint64_t la, const ui
 __device__ __forceinline__ int cmp_ids(const CompactArgs& a, uint32_t x, uint32_t y) {
     const uint64_t bx = a.offsets[x], by = a.offsets[y];
     return cmp_keys(a.keys + bx, a.offsets[x + 1] - bx, a.keys + by, a.offsets[y + 1] - by);
-}
-
-// Big-endian 8-byte prefix of a key (zero-padded): prefixes order keys except on ties.
-__device__ __forceinline__ uint64_t key_prefix8(const uint8_t* k, uint64_t len) {
-    if (len >= 8) return ld_be64(k);
-    uint64_t w = 0;
-    for (uint64_t i = 0; i < len; ++i) w |= (uint64_t)k[i] << (56 - 8 * i);
-    return w;
 }
 
 // (prefix, id) order: prefixes first, the full keys only on a prefix tie.

@@ -21,10 +21,8 @@
 //                      A workgroup looks up kMemKeys = 1024 keys, four per lane, so a staged sample is
 //                      read by 1024 searches.
 //
-// Precedence (per key, the same in both): the gc layer decides only with a live entry whose log
-// header (vbf_vlog.hip's window tests) is a live value or BAD; the active memtable decides whatever
-// it holds; the read-only tables fold by strictly greater signed time from 0, the earlier table on a
-// tie; what is left at time <= 0 is not found.
+// Precedence (per key, the same in both): gc_stands / fold_hit / fold_close of vbf_store_fold.hpp,
+// shared with the whole-store range scan.
 //
 //   k_store_cand  : rows of the SST candidate matrix of the keys a memtable decided are zeroed.
 //   k_store_merge : a memtable's answer stands, otherwise the tables' with layer = 2^31 | table.
@@ -33,6 +31,7 @@
 
 #include "vbf_kernels.hpp"
 #include "vbf_keycmp.hpp"
+#include "vbf_store_fold.hpp"
 
 namespace vbf {
 
@@ -41,7 +40,6 @@ namespace {
 constexpr uint32_t kMemSample = 4096;  // pfx words staged per layer: 32 KiB of LDS
 constexpr uint32_t kMemPer = 4;        // keys per lane
 constexpr uint32_t kMemKeys = 256 * kMemPer;
-constexpr uint64_t kLogHdr = 17;
 
 __global__ __launch_bounds__(256) void k_mem_prefix(const uint8_t* keys, const uint64_t* off, uint64_t n,
                                                     uint64_t* pfx) {
@@ -87,43 +85,6 @@ __device__ __forceinline__ uint64_t find_pfx(const MemDesc& d, const Query& q, u
         else hi = mid;
     }
     return d.n;
-}
-
-// vbf_vlog_get_*'s window tests on the header at `off`: true when the gc entry's hit stands (a live
-// value, or BAD, which the value fetch reports), false for NONE and TOMBSTONE (search_gc_entries'
-// Ok(None): the lookup falls through).
-__device__ __forceinline__ bool gc_stands(const MemGetArgs& a, uint64_t off) {
-    const uint64_t end = a.log_base + a.log_len;
-    if (off >= end) return false;
-    if (off < a.log_base || off + kLogHdr > end) return true;
-    const uint8_t* e = a.log + (off - a.log_base);
-    uint32_t kl, vl;
-    __builtin_memcpy(&kl, e, 4);
-    __builtin_memcpy(&vl, e + 4, 4);
-    if (off + kLogHdr + kl + vl > end) return true;  // at most 2^32 + 2^33: no wrap in 64 bits
-    return e[16] != 1;
-}
-
-struct Fold {
-    uint8_t found;
-    bool decided;  // by the gc layer or the active memtable: no later layer is asked
-    uint32_t layer, val;
-    int64_t time;
-};
-
-// Layer L's entry e (a hit) folded into f, by the rules of store.rs:445-472.
-__device__ __forceinline__ void fold_hit(const MemGetArgs& a, const MemDesc& d, uint32_t L, uint64_t e, Fold& f) {
-    const bool tomb = d.tomb[e] != 0;  // as the encoder writes it
-    const uint32_t val = d.val[e];
-    const int64_t t = d.created[e];
-    if (L == 0) {
-        if (tomb || !gc_stands(a, val)) return;
-        f = Fold{1, true, 0, val, t};
-    } else if (L == 1) {
-        f = Fold{(uint8_t)(tomb ? 2 : 1), true, 1, val, t};
-    } else if (t > f.time) {
-        f = Fold{(uint8_t)(tomb ? 2 : 1), false, L, val, t};
-    }
 }
 
 __device__ __forceinline__ void store(const MemGetArgs& a, uint64_t j, const Fold& f) {
@@ -200,7 +161,7 @@ __global__ __launch_bounds__(256) void k_mem_get(MemGetArgs a) {
     for (uint32_t r = 0; r < kMemPer; ++r) {
         const uint64_t j = base + (uint64_t)r * 256;
         if (j >= a.n) continue;
-        if (!f[r].decided && f[r].time <= 0) f[r].found = 0;  // found_in_table: only a time above 0 counts
+        fold_close(f[r]);
         store(a, j, f[r]);
     }
 }

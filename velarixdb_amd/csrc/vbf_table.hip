@@ -121,8 +121,7 @@ __global__ __launch_bounds__(256) void k_table_get(TableGetArgs a) {
     const uint64_t qb = a.offsets ? a.offsets[j] : j * a.stride;
     const uint64_t ql = a.offsets ? a.offsets[j + 1] - qb : a.stride;
     const uint8_t* q = a.keys + qb;
-    uint64_t best = 0;  // default_datetime(): only a strictly newer entry replaces the winner
-    uint32_t bval = 0, bidx = 0xFFFFFFFFu, bfound = 0;
+    TabFold f{0, 0, 0xFFFFFFFFu, 0};  // default_datetime(): only a strictly newer entry replaces the winner
     for (uint32_t t = 0; t < a.nsst; ++t) {
         if (a.cand && !a.cand[j * a.nsst + t]) continue;
         const TableDesc& d = a.tab[t];
@@ -131,21 +130,13 @@ __global__ __launch_bounds__(256) void k_table_get(TableGetArgs a) {
         if (lo == d.nblocks) continue;
         // block step: equality inside that block
         const BlockPos at = block_lower(d, lo, q, ql);
-        const uint8_t* hit = at.hit;
-        const uint32_t hl = at.hit_len;
-        if (!hit) continue;
-        const uint64_t created = ld8(hit + 8 + hl);
-        if (created > best) {
-            best = created;
-            bval = ld4(hit + 4 + hl);
-            bidx = t;
-            bfound = hit[16 + hl] == 1 ? 2u : 1u;
-        }
+        if (!at.hit) continue;
+        fold_table_hit(f, t, at.hit, at.hit_len);
     }
-    if (a.found) a.found[j] = (uint8_t)bfound;
-    if (a.table_idx) a.table_idx[j] = bidx;
-    if (a.val_off) a.val_off[j] = bval;
-    if (a.created) a.created[j] = best;
+    if (a.found) a.found[j] = (uint8_t)f.found;
+    if (a.table_idx) a.table_idx[j] = f.idx;
+    if (a.val_off) a.val_off[j] = f.val;
+    if (a.created) a.created[j] = f.best;
 }
 
 }  // namespace

@@ -42,41 +42,7 @@ namespace {
 
 constexpr uint32_t kScanKeyLanes = 8;  // lanes per key in k_scan_keys
 
-// The rank of the first entry of `d` with key >= q: the index step, the block step, then ebase.
-// No index record >= q (or an empty table): every entry is smaller, the rank is the entry count.
-// eq: the table holds q, at `hit` (the first entry > q then has rank + 1); else hit = nullptr.
-struct RankPos {
-    uint64_t rank;
-    const uint8_t* hit;
-    uint32_t hit_len;
-    bool eq;
-};
-__device__ __forceinline__ RankPos rank_lower(const TableDesc& d, const uint8_t* q, uint64_t ql) {
-    RankPos r{0, nullptr, 0, false};
-    if (d.nblocks != 0) {
-        const uint64_t b = index_lower(d, q, ql);
-        r.rank = d.ebase[b];
-        if (b != d.nblocks) {
-            const BlockPos at = block_lower(d, b, q, ql);
-            r.rank += at.at;
-            r.hit = at.hit;
-            r.hit_len = at.hit_len;
-            r.eq = at.eq;
-        }
-    }
-    return r;
-}
-
-// The largest i in [0, n) with a[i] <= v, for nondecreasing a with a[0] <= v < a[n].
-__device__ __forceinline__ uint64_t last_le(const uint64_t* a, uint64_t n, uint64_t v) {
-    uint64_t lo = 0, hi = n;  // a[lo] <= v < a[hi]
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+// rank_lower and last_le: vbf_table_search.hpp (shared with the whole-store scan).
 
 __global__ __launch_bounds__(256) void k_scan_bounds(TableScanArgs a) {
     const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;

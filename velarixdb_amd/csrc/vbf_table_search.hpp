@@ -90,4 +90,58 @@ __device__ __forceinline__ BlockPos block_lower(const TableDesc& d, uint64_t b, 
     return BlockPos{el, fl, found, eq};
 }
 
+// The fold of DataStore::search_key_in_sstables (src/db/store.rs:579-612) over the tables in the
+// caller's order: the winner starts at default_datetime() (0) and only a strictly newer entry
+// replaces it, so a tie goes to the earlier table and created_at == 0 never wins.  found: 0 no
+// winner, 1 live, 2 tombstone.  Starts as TabFold{0, 0, 0xFFFFFFFFu, 0}.
+struct TabFold {
+    uint64_t best;
+    uint32_t val, idx, found;
+};
+__device__ __forceinline__ void fold_table_hit(TabFold& f, uint32_t t, const uint8_t* hit, uint32_t hl) {
+    const uint64_t created = ld8(hit + 8 + hl);
+    if (created > f.best) {
+        f.best = created;
+        f.val = ld4(hit + 4 + hl);
+        f.idx = t;
+        f.found = hit[16 + hl] == 1 ? 2u : 1u;
+    }
+}
+
+// The rank of the first entry of `d` with key >= q: the index step, the block step, then ebase.
+// No index record >= q (or an empty table): every entry is smaller, the rank is the entry count.
+// eq: the table holds q, at `hit` (the first entry > q then has rank + 1); else hit = nullptr.
+struct RankPos {
+    uint64_t rank;
+    const uint8_t* hit;
+    uint32_t hit_len;
+    bool eq;
+};
+__device__ __forceinline__ RankPos rank_lower(const TableDesc& d, const uint8_t* q, uint64_t ql) {
+    RankPos r{0, nullptr, 0, false};
+    if (d.nblocks != 0) {
+        const uint64_t b = index_lower(d, q, ql);
+        r.rank = d.ebase[b];
+        if (b != d.nblocks) {
+            const BlockPos at = block_lower(d, b, q, ql);
+            r.rank += at.at;
+            r.hit = at.hit;
+            r.hit_len = at.hit_len;
+            r.eq = at.eq;
+        }
+    }
+    return r;
+}
+
+// The largest i in [0, n) with a[i] <= v, for nondecreasing a with a[0] <= v < a[n].
+__device__ __forceinline__ uint64_t last_le(const uint64_t* a, uint64_t n, uint64_t v) {
+    uint64_t lo = 0, hi = n;  // a[lo] <= v < a[hi]
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (a[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 }  // namespace vbf
